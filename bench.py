@@ -2,6 +2,14 @@
 """Benchmark of the MI355X tree-DPF PIR answer path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c24|c2|c3|c5|c4|c3b]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes their answers if --dump-outputs is
+given, and prints the result line (value, ms_per_step, the roofline of the timed launch).
+Everything else described below -- `single_query`, the correctness checks at full size, the
+extra workloads on the same line, the 1-GPU reference of an N-GPU run, the traced launch and
+the CPU baselines -- runs only with --full.  Keys and shard are seeded: the same arguments
+give the same queries and the same answers in every run.
 
 A step = one PIR query answered against the device-resident shard: key parse -> DPF
 full-domain evaluation (AES-128 PRG tree) -> GF(2^8) inner product over every record ->
@@ -54,6 +62,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s; 6.29 
 HBM_READ_MEASURED_GBS = 6762.0
 GIB = float(1 << 30)
 SHARD_SEED = 0xC0FFEE
+KEY_SEED = 0x5EEDED  # query indices and DPF key seeds
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: the most it writes
 
 CONFIGS = {
     # name: (log records, record bytes, parties, rounds, strong, workload text)
@@ -522,6 +532,16 @@ def r5(x):
     return round(float(x), 5)
 
 
+def dump_outputs(dirname, answers):
+    """--dump-outputs: the timed steps' answers (steps first, one value per answer byte) as
+    DIR/answers.npy in float32 -- the last steps that fit DUMP_LIMIT_BYTES, the last one always."""
+    a = np.asarray(answers)
+    per_step = max(1, a[0].size * 4)
+    keep = max(1, min(len(a), DUMP_LIMIT_BYTES // per_step))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "answers.npy"), a[len(a) - keep:].astype(np.float32))
+
+
 def trace_stats(eng, keys, nk):
     """One traced k_query launch (pir_engine_trace_query: per-workgroup wall-clock stamps and
     s_memtime shader-clock stamps) of a queue of nk of `keys`, after the timed legs: the shader
@@ -620,7 +640,16 @@ def main():
     ap.add_argument("--config", default=None,
                     choices=sorted(CONFIGS) + sorted(BATCH_CONFIGS) + sorted(COEF_CONFIGS) + sorted(MP_CONFIGS) + sorted(CD_CONFIGS),
                     help="default: c24 on one GPU, c4 (split shard) on several")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can carry: the "
+                         "correctness checks at full size, the one-launch-per-query and host-API "
+                         "rates, the traced launch, the other configs' legs, the setup and thread "
+                         "legs and the CPU baselines (a plain run times the steps and stops)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the answers of the timed steps to DIR/answers.npy (float32, one "
+                         "value per answer byte); keys and shard are seeded, so two runs with the "
+                         "same arguments write the same answers")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=20.0,
                     help="seconds of single-core reference work (at least one full query)")
     ap.add_argument("--cpu-cores", type=int, default=-1,
@@ -654,7 +683,7 @@ def main():
     ctx.rehearsal = ctx.host_fold = rehearsal
 
     import erasurecodedpir_amd as pir
-    from erasurecodedpir_amd.dist import broadcast_bytes, log2_exact
+    from erasurecodedpir_amd.dist import log2_exact
 
     config = args.config or ("c24" if world == 1 else "c4")
     if config in BATCH_CONFIGS:
@@ -667,9 +696,7 @@ def main():
     g = log2_exact(world)
     n = n_cfg if strong else n_cfg + g  # logical tree depth
     W, K = args.warmup, args.steps
-    seed = int.from_bytes(broadcast_bytes(os.urandom(8) if rank == 0 else None)
-                          if world > 1 else os.urandom(8), "little")
-    rng = np.random.default_rng(seed)
+    rng = np.random.default_rng(KEY_SEED)  # the same queries on every rank and in every run
     keyset, fcw = make_keys(pir, n, p, nq, W + K, rng, local)
 
     eng = pir.Engine(p, 1, n, efs, nq, device=local, log_num_partitions=g, partition_index=rank)
@@ -678,10 +705,13 @@ def main():
     if world > 1 and not rehearsal:
         comm_err = attach_or_fallback(pir, eng, world, rank)
         ctx.host_fold = comm_err is not None
-    m = measure(ctx, eng, [ks[0] for _, ks in keyset], W, K, single=not args.queue_only)
+    full = args.full and not args.queue_only
+    m = measure(ctx, eng, [ks[0] for _, ks in keyset], W, K, single=full)
     ms = m["ms"]
     shard_bytes = float(1 << n) * efs  # logical shard (all ranks)
     value = shard_bytes / GIB / (ms / 1e3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["answers"])
     if args.queue_only:
         if rank == 0:
             print(json.dumps({"metric": METRIC, "value": round(value, 3), "unit": "GiB/s",
@@ -695,30 +725,13 @@ def main():
         return
 
     timed = keyset[W:]
-    # PIR correctness at full size on every rank (the party-2 answers come from the same
-    # resident shard, answered as party 2)
-    pir_ok = pir_check(ctx, eng, timed[:4] if p == 2 else timed[:2], fcw, m["answers"], n, g,
-                       parties=sorted({2, p}))
-    # host API (key H2D + answer D2H + sync): the PCIe-inclusive rate
     k0 = timed[0][1][0]
-    incl_steps = min(20, K)
-    t1 = time.perf_counter()
-    for _ in range(incl_steps):
-        a1 = eng.answer(k0)
-    a1 = ctx.fold(a1)
-    incl_ms = (time.perf_counter() - t1) / incl_steps * 1e3
-    same = bool(np.array_equal(a1, m["singles"][0]))
-    queue_same = bool(np.array_equal(m["answers"], m["singles"]))
-
     ph = m["phases"]
     local_bytes = float(eng.num_rows) * efs
     kern_ms = ph.get("scan", float("nan"))  # the k_query launch (all K queries)
     path = {2.0: "k_query", 1.0: "k_fused", 0.0: "k_expand+k_scan"}.get(ph.get("fused"), "?")
-    rl = roofline(kern_ms, local_bytes, K, config, world)
+    rl = roofline(kern_ms, local_bytes, K, config, world)  # from the timed launch's own events
     rl["kernel"] = rl["kernel"].replace("k_query", path)
-    if world == 1:  # the clock this box ran the kernel at (a traced queue of 2 after the timing)
-        ts = trace_stats(eng, [ks[0] for _, ks in keyset[W:]], 2)
-        rl["shader_clock_ghz"] = ts["shader_clock_ghz"] if ts else None
     out = {
         "metric": METRIC,
         "value": round(value, 3),
@@ -748,18 +761,6 @@ def main():
         },
         "roofline": rl,
         "roofline_valu": _valu_roofline(config, world, kern_ms, K, float(eng.num_rows)),
-        "single_query": {
-            "ms_per_query": r5(m["ms1"]),
-            "value": round(shard_bytes / GIB / (m["ms1"] / 1e3), 3),
-            "unit": "GiB/s",
-            "note": "answer_dev per step (one launch per query, nothing queued behind it)",
-            **single_phases(m["phases1"], m["ms1"]),
-        },
-        "inclusive_h2d_key_d2h_answer": {"ms_per_query": round(incl_ms, 4),
-                                         "value": round(shard_bytes / GIB / (incl_ms / 1e3), 3),
-                                         "unit": "GiB/s"},
-        "parity": {"pir_record_recovered": pir_ok, "host_api_equals_device_api": same,
-                   "queue_equals_one_at_a_time": queue_same},
     }
     if world > 1:  # per-rank kernel and exchange times of the timed queue
         rl_rank = roofline(kern_ms, local_bytes, K, config, world)  # this rank's own kernel time
@@ -773,6 +774,45 @@ def main():
         dist.all_gather_object(allr, mine)
         out["per_rank"] = allr
         out.update(exchange_fields(allr, world, ctx.host_fold, comm_err))
+    if not full:  # a plain run: the timed steps and their line
+        eng.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # PIR correctness at full size on every rank (the party-2 answers come from the same
+    # resident shard, answered as party 2)
+    pir_ok = pir_check(ctx, eng, timed[:4] if p == 2 else timed[:2], fcw, m["answers"], n, g,
+                       parties=sorted({2, p}))
+    # host API (key H2D + answer D2H + sync): the PCIe-inclusive rate
+    incl_steps = min(20, K)
+    t1 = time.perf_counter()
+    for _ in range(incl_steps):
+        a1 = eng.answer(k0)
+    a1 = ctx.fold(a1)
+    incl_ms = (time.perf_counter() - t1) / incl_steps * 1e3
+    same = bool(np.array_equal(a1, m["singles"][0]))
+    queue_same = bool(np.array_equal(m["answers"], m["singles"]))
+    if world == 1:  # the shader clock of the kernel (a traced queue of 2 after the timing)
+        ts = trace_stats(eng, [ks[0] for _, ks in keyset[W:]], 2)
+        rl["shader_clock_ghz"] = ts["shader_clock_ghz"] if ts else None
+    out.update({
+        "single_query": {
+            "ms_per_query": r5(m["ms1"]),
+            "value": round(shard_bytes / GIB / (m["ms1"] / 1e3), 3),
+            "unit": "GiB/s",
+            "note": "answer_dev per step (one launch per query, nothing queued behind it)",
+            **single_phases(m["phases1"], m["ms1"]),
+        },
+        "inclusive_h2d_key_d2h_answer": {"ms_per_query": round(incl_ms, 4),
+                                         "value": round(shard_bytes / GIB / (incl_ms / 1e3), 3),
+                                         "unit": "GiB/s"},
+        "parity": {"pir_record_recovered": pir_ok, "host_api_equals_device_api": same,
+                   "queue_equals_one_at_a_time": queue_same},
+    })
     cpu_path = None
     threads_leg = rank == 0 and world == 1 and not args.no_extras and config == "c24"
     if rank == 0 and world == 1 and (not args.no_cpu or threads_leg):
@@ -1275,13 +1315,18 @@ def run_coefs(args, ctx, config):
     dt = ctx.timed(eng, lambda: [eng.answer_coefs_dev(d_c + (i % nkeys) * nq * N, N, 0, N,
                                                       d_r + i * nq * efs) for i in range(K)])
     ms = dt / K * 1e3
-    # correctness at full size: one coefficient changed by x moves its round's answer by x*record
-    host = eng.d2h(d_c, nq * N).reshape(nq, N)
-    base = eng.answer_coefs(host)
-    i, x = N // 3, 0x35
-    host[nq - 1, i] ^= x
-    moved = eng.answer_coefs(host)
-    ok = bool(np.array_equal((base ^ moved)[nq - 1], _gf_table(x)[eng.shard_row(i)]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng.d2h(d_r, K * nq * efs).reshape(K, nq, efs))
+    ok = None
+    if args.full:
+        # correctness at full size: one coefficient changed by x moves its round's answer by
+        # x*record
+        host = eng.d2h(d_c, nq * N).reshape(nq, N)
+        base = eng.answer_coefs(host)
+        i, x = N // 3, 0x35
+        host[nq - 1, i] ^= x
+        moved = eng.answer_coefs(host)
+        ok = bool(np.array_equal((base ^ moved)[nq - 1], _gf_table(x)[eng.shard_row(i)]))
     eng.close()
     gib = float(N) * efs / GIB
     algo = float(N) * (efs + nq)  # shard + the query's coefficients
@@ -1295,7 +1340,7 @@ def run_coefs(args, ctx, config):
                         "unit": "GB/s", "frac": round(algo / (ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
                         "traffic": None, "algorithmic_bytes_per_query": int(algo),
                         "note": "wall time per query over the device work of all three launches"},
-           "parity": {"coefficient_linearity": ok}}
+           **({"parity": {"coefficient_linearity": ok}} if args.full else {})}
     if ctx.rank == 0:
         print(json.dumps(out), flush=True)
 
@@ -1348,24 +1393,9 @@ def run_mp(args, ctx, config):
     dt = ctx.timed(eng, lambda: [ans_dev(d_k + (i % nkeys) * eb, d_r + i * nrk * efs)
                                  for i in range(K)])
     ms = dt / K * 1e3
-    # correctness at full size: flipping cw[j][x] by d moves share a's answer by
-    # d * XOR of the records i*mu + x of the rows whose toggle (a, i, j) is set
-    j, x, d = 1, 777, 0x5A
-    cwo = tog + nrk * nu * p2
-    k0 = keys[0].copy()
-    base = ans(k0)
-    k0[cwo + j * mu + x] ^= d
-    moved = ans(k0)
-    tab = _gf_table(d)
-    ok = True
-    for a in range(nrk):
-        acc = np.zeros(efs, np.uint8)
-        for i in range(nu):
-            if keys[0][tog + a * nu * p2 + i * p2 + j]:
-                acc ^= eng.shard_row(i * mu + x)
-        ok &= bool(np.array_equal((base ^ moved)[a], tab[acc]))
-    dev0 = eng.d2h(d_r, nrk * efs).reshape(nrk, efs)
-    ok_dev = bool(np.array_equal(dev0, ans(keys[0])))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng.d2h(d_r, K * nrk * efs).reshape(K, nrk, efs))
+    parity = mp_check(eng, ans, keys, d_r, nrk, nu, p2, mu, tog, efs) if args.full else None
     eng.close()
     gib = float(N) * efs / GIB
     algo = float(N) * efs + eb  # shard + the key
@@ -1392,16 +1422,40 @@ def run_mp(args, ctx, config):
                         "traffic": traffic, "traffic_source": tsrc,
                         "algorithmic_bytes_per_query": int(algo),
                         "note": "wall time per query over the device work of the launches"},
-           "parity": {"correction_word_linearity": ok, "device_equals_host_api": ok_dev}}
+           **({"parity": parity} if args.full else {})}
     if ctx.rank == 0:
         print(json.dumps(out), flush=True)
+
+
+def mp_check(eng, ans, keys, d_r, nrk, nu, p2, mu, tog, efs):
+    """run_mp's correctness at full size: flipping cw[j][x] by d moves share a's answer by
+    d * XOR of the records i*mu + x of the rows whose toggle (a, i, j) is set; and the first
+    timed step's device answer equals the host API's."""
+    j, x, d = 1, 777, 0x5A
+    cwo = tog + nrk * nu * p2
+    k0 = keys[0].copy()
+    base = ans(k0)
+    k0[cwo + j * mu + x] ^= d
+    moved = ans(k0)
+    tab = _gf_table(d)
+    ok = True
+    for a in range(nrk):
+        acc = np.zeros(efs, np.uint8)
+        for i in range(nu):
+            if keys[0][tog + a * nu * p2 + i * p2 + j]:
+                acc ^= eng.shard_row(i * mu + x)
+        ok &= bool(np.array_equal((base ^ moved)[a], tab[acc]))
+    dev0 = eng.d2h(d_r, nrk * efs).reshape(nrk, efs)
+    ok_dev = bool(np.array_equal(dev0, ans(keys[0])))
+    return {"correction_word_linearity": ok, "device_equals_host_api": ok_dev}
 
 
 def run_batch(args, ctx, config):
     """A step = `batch` keys answered against the device-resident shard (answer_batch_dev: one
     shard pass per group of keys, one DPF tree per key).  value = effective GiB/s = keys x
     logical shard bytes / time (every key's answer covers the whole shard)."""
-    out = measure_batch(args.steps, args.warmup, ctx, config)
+    out = measure_batch(args.steps, args.warmup, ctx, config, full=args.full,
+                        dump=args.dump_outputs)
     if ctx.rank == 0:
         print(json.dumps(out), flush=True)
     if ctx.world > 1:
@@ -1409,9 +1463,11 @@ def run_batch(args, ctx, config):
         ctx.dist.destroy_process_group()
 
 
-def measure_batch(steps, warmup, ctx, config):
+def measure_batch(steps, warmup, ctx, config, full=True, dump=None):
+    """full=False: the timed steps only (no phase profile of a lone key, no PIR check);
+    dump: --dump-outputs' directory."""
     import erasurecodedpir_amd as pir
-    from erasurecodedpir_amd.dist import broadcast_bytes, log2_exact
+    from erasurecodedpir_amd.dist import log2_exact
 
     world, rank, local = ctx.world, ctx.rank, ctx.local
     n_local, efs, p, nq, nk, workload = BATCH_CONFIGS[config]
@@ -1425,8 +1481,7 @@ def measure_batch(steps, warmup, ctx, config):
         # no host-fold variant of the batched answer: a rank that cannot join RCCL ends the run
         os.environ["PIR_BENCH_NO_FALLBACK"] = "1"
         attach_or_fallback(pir, eng, world, rank)
-    rng = np.random.default_rng(int.from_bytes(
-        broadcast_bytes(os.urandom(8) if rank == 0 else None) if world > 1 else os.urandom(8), "little"))
+    rng = np.random.default_rng(KEY_SEED)  # the same keys on every rank and in every run
     keyset, fcw = make_keys(pir, n, p, nq, nk, rng, local)
     d_keys = eng.alloc_dev(eng.key_len * nk)
     d_res = eng.alloc_dev(eng.answer_bytes * nk)
@@ -1437,20 +1492,23 @@ def measure_batch(steps, warmup, ctx, config):
     dt = ctx.timed(eng, lambda: [eng.answer_batch_dev(d_keys, nk, d_res) for _ in range(steps)])
     eng.set_profiling(0)
     ms = dt / steps * 1e3
-    alone = eng.profile_phases(d_keys, 5)
     got = eng.d2h(d_res, eng.answer_bytes * nk).reshape(nk, nq, efs)
-    # correctness at full size: party-1 batch ^ party-2 batch == finalCW * record, every key
-    eng.set_party(2)
-    got2 = eng.answer_batch([ks[1] for _, ks in keyset])
-    eng.set_party(1)
-    tab = _gf_table(int(fcw[0]))
-    ok = True
-    for q, (i, _) in enumerate(keyset):
-        owner = i >> (n - g) if g else 0
-        rec = eng.shard_row(i - owner * eng.num_rows) if rank == owner else None
-        if world > 1:
-            rec = broadcast_from(rec, owner, efs)
-        ok &= bool(np.array_equal(got[q][0] ^ got2[q][0], tab[rec]))
+    if dump and rank == 0:
+        dump_outputs(dump, got[None])  # every timed step answers the same nk keys
+    if full:
+        alone = eng.profile_phases(d_keys, 5)
+        # correctness at full size: party-1 batch ^ party-2 batch == finalCW * record, every key
+        eng.set_party(2)
+        got2 = eng.answer_batch([ks[1] for _, ks in keyset])
+        eng.set_party(1)
+        tab = _gf_table(int(fcw[0]))
+        ok = True
+        for q, (i, _) in enumerate(keyset):
+            owner = i >> (n - g) if g else 0
+            rec = eng.shard_row(i - owner * eng.num_rows) if rank == owner else None
+            if world > 1:
+                rec = broadcast_from(rec, owner, efs)
+            ok &= bool(np.array_equal(got[q][0] ^ got2[q][0], tab[rec]))
     shard_bytes = float(1 << n) * efs
     out = {
         "metric": METRIC,
@@ -1467,9 +1525,10 @@ def measure_batch(steps, warmup, ctx, config):
         "ms_per_key": round(ms / nk, 5),
         "keys_per_s": round(nk / (ms / 1e3), 1),
         "shard_passes_per_step": -(-nk // eng.batch_group),
-        "single_key_phases_alone_ms": {k: r5(v) for k, v in alone.items()},
-        "parity": {"pir_record_recovered_all_keys": ok},
     }
+    if full:
+        out["single_key_phases_alone_ms"] = {k: r5(v) for k, v in alone.items()}
+        out["parity"] = {"pir_record_recovered_all_keys": ok}
     eng.close()
     return out
 

@@ -72,6 +72,20 @@ def test_rccl_self_check_fields():
     assert not reh["rccl_ranks_ok"] and reh["exchange"].endswith("(rehearsal)")
 
 
+def test_dump_outputs_keeps_the_last_steps(monkeypatch, tmp_path):
+    """--dump-outputs: answers.npy holds the timed steps' answer bytes as float32, and under the
+    size limit the steps kept are the last ones."""
+    import bench
+    ans = np.random.default_rng(3).integers(0, 256, (7, 2, 64), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), ans)
+    got = np.load(tmp_path / "a" / "answers.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, ans)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * 2 * 64 * 4 + 5)
+    bench.dump_outputs(str(tmp_path / "b"), ans)
+    got = np.load(tmp_path / "b" / "answers.npy")
+    assert got.nbytes <= bench.DUMP_LIMIT_BYTES and np.array_equal(got, ans[-3:])
+
+
 class _FakeTraceEngine:
     """trace_query's layout (include/pir_engine.h): wall stamps in us, shader-clock columns in
     ticks / 100."""

@@ -9,7 +9,8 @@
 #   env:K=V[,K=V...]      export variables for the steps after it (env: alone clears nothing)
 #   pytest[:ARGS]         python -m pytest -m gpu ARGS (default: tests) -> TAG_pytest.log
 #   smoke                 __graft_entry__.smoke()                        -> TAG_smoke.log
-#   bench[:ARGS]          python bench.py ARGS (spaces as '+')            -> TAG_bench.jsonl
+#   bench[:ARGS]          python bench.py ARGS (spaces as '+'; --full for
+#                         the line with every leg)                         -> TAG_bench.jsonl
 #   prof:NAME[:ARGS]      rocprofv3 --kernel-trace --stats of bench.py ARGS -> TAG_prof_NAME/
 #   py:SCRIPT[:ARGS]      python tools/SCRIPT ARGS                         -> TAG_SCRIPT.log
 #   sha                   sha256 of the libraries                          -> TAG_lib_sha256.txt
