@@ -137,6 +137,9 @@ struct pir_engine {
   size_t bpart_cap = 0, bgather_cap = 0;
   int batch_group = 0;          // keys per shard pass (0: automatic; $PIR_BATCH_G)
   int last_batch_group = 0;
+  int stream_share = 1;         // $PIR_STREAM_SHARE: 0 never, 1 stream_share_policy, 2 wherever supported
+  int stream_group = 0;         // $PIR_STREAM_G: keys per pass of a shared queue (0: the policy's)
+  bool stream_narrow = false;   // $PIR_STREAM_NARROW=1: narrower scans for short groups (diagnostics)
   int batch_scan_bpc = 2;       // scan workgroups per CU in batched answers ($PIR_BATCH_SCAN_BPC)
   int batch_k_last = -1;        // levels of the batched leaf stage (-1: make_plan's; $PIR_BATCH_KLAST)
   uint8_t* d_result = nullptr;  // nq*efs (host-API staging)
@@ -171,8 +174,13 @@ struct pir_engine {
   std::mutex mu;
   uint64_t byz_counter = 0;
   // profiling: a ring of event sets, one per answer, read back after a sync
+  // fused: the path of the slot's answer, which decides the events recorded in it (2: k_query,
+  // and with queue set a shared queue of fused == 0: EV_START, EV_SCAN_B, EV_SCAN_E, EV_RED,
+  // EV_END; else every event up to `chunks` leaf / scan pairs)
   struct ProfSlot {
     hipEvent_t ev[kNumEv];
+    int fused = 0, chunks = 1;
+    bool queue = false;
   };
   std::vector<ProfSlot> prof;
   int prof_next = 0, prof_count = 0;
@@ -438,12 +446,87 @@ int answer_core(pir_engine* e, const uint8_t* d_raw, int log_parts_total, uint64
 }
 
 // keys answered per shard pass: G keys x nrp share bytes per record (a power of two <= 16)
-int batch_group(const pir_engine* e) {
-  const int maxg = 16 / e->nrp;
-  int g = e->batch_group > 0 ? e->batch_group : 8 / std::min(e->nrp, 8);
-  g = std::max(1, std::min(g, maxg));
+int clamp_group(const pir_engine* e, int g) {
+  g = std::max(1, std::min(g, 16 / e->nrp));
   while (g & (g - 1)) g &= g - 1;  // power of two
   return g;
+}
+int batch_group(const pir_engine* e) {
+  return clamp_group(e, e->batch_group > 0 ? e->batch_group : 8 / std::min(e->nrp, 8));
+}
+
+// Keys per shard pass of a queue (answer_stream) by default; 0: every query its own pass in
+// k_query.  A pure function of the shape, enabled only where the shared queue measured faster
+// than k_query's queue of the parent build on the same machine, alternating runs
+// (profiles/stream_share/README.md).
+int stream_share_policy(int rounds, uint32_t pitch, uint64_t rows, int nk) {
+  // measured: one round, 8 keys per pass (k_scan_t), 2^20 / 2^24 / 2^27 rows of 1 KiB and 2^24
+  // of 256 B, all 1.5-1.8x k_query's queue of 20; 4 and 2 keys per pass gain less, 16 lose; a
+  // pass of 8 key slots costs about two of k_query's, so queues of fewer than 4 keys stay there;
+  // five rounds (two keys per pass) lose by 15x
+  if (rounds != 1 || nk < 4) return 0;
+  if (pitch < 256 || pitch > 1024 || pitch % 256 != 0 || rows < (1ull << 20)) return 0;
+  return 8;
+}
+
+// the group size answer_stream uses for a queue of nk keys (0: k_query).  $PIR_STREAM_SHARE: 0
+// never shares, 1 (default) follows stream_share_policy, 2 shares wherever the batched path
+// takes the shape; $PIR_STREAM_G overrides the group size (diagnostics)
+int stream_group(const pir_engine* e, int nk) {
+  const auto& c = e->cfg;
+  if (e->stream_share == 0 || nk < 2 || c.is_byzantine || e->nrp > 8) return 0;
+  int g = stream_share_policy(c.num_rounds, e->pitch, e->rows, nk);
+  if (g == 0 && e->stream_share < 2) return 0;
+  if (g == 0) g = std::max(2, 8 / e->nrp);
+  if (e->stream_group > 0) g = e->stream_group;
+  g = clamp_group(e, g);
+  return g >= 2 ? g : 0;
+}
+
+// the scan of a group of gw <= G key slots (gw * nrp rounds); key-major shares for k_scan_t,
+// which a narrowed group (gw < G) takes wherever it can
+pir::ScanShape group_scan_shape(const pir_engine* e, uint64_t nleaves, int gw, int G, bool* kmaj) {
+  pir::ScanShape sh = pir::make_scan_shape(nleaves, e->pitch, gw * e->nrp, e->num_cus,
+                                           e->batch_scan_bpc, gw < G);
+  // k_scan_t reads the group's shares key-major (key g's nrp bytes of leaf i at g * nleaves *
+  // nrp + i * nrp), so each tree's leaf stage writes its shares contiguously (packed 16-byte
+  // stores); the other scans read them interleaved per record (cb[i][W], key g at g * nrp).
+  // One key slot: the two layouts are the same one
+  *kmaj = sh.tfold && gw > 1 && !(getenv("PIR_BATCH_KMAJOR") && atoi(getenv("PIR_BATCH_KMAJOR")) == 0);
+  if (*kmaj) {
+    sh.ckey = (uint32_t)e->nrp;
+    sh.ckoff = (uint64_t)nleaves * e->nrp;
+  }
+  return sh;
+}
+
+// the tree plan and super-group of a batched answer
+pir::TreePlan batch_plan(const pir_engine* e, int log_parts_total, uint64_t prefix, int G, int* FB) {
+  const auto& c = e->cfg;
+  const pir::TreePlan pl = pir::make_plan(c.log_num_records, log_parts_total, prefix, e->batch_k_last, c.num_parties, 8);
+  // super-group: as many keys as kBatchNodeBytes of upper-level nodes hold (a multiple of G)
+  const uint64_t per_key = 2 * pl.max_nodes * (sizeof(uint4) + sizeof(uint32_t));
+  int fb = (int)std::min<uint64_t>(kFrontBatch, std::max<uint64_t>(1, kBatchNodeBytes / per_key));
+  *FB = std::max(G, fb / G * G);
+  return pl;
+}
+
+// every buffer a batched answer of nk keys, G per pass, touches (narrow: a ragged last group
+// may take a narrower scan with its own slab shape)
+int ensure_batched(pir_engine* e, const pir::TreePlan& pl, int FB, int nk, int G, bool narrow) {
+  size_t slab = 0;
+  for (int gw = narrow ? 1 : G; gw <= G; gw *= 2) {
+    bool km;
+    const pir::ScanShape sh = group_scan_shape(e, pl.nleaves, gw, G, &km);
+    slab = std::max(slab, (size_t)sh.grid.x * sh.grid.y * sh.slab_bytes);
+  }
+  int rc = ensure_slabs(e, slab);
+  if (!rc) rc = ensure_buf(&e->d_cb, &e->cb_cap, 2 * (size_t)pl.nleaves * G * e->nrp);
+  if (!rc) rc = ensure_batch(e, nk);
+  if (!rc) rc = ensure_nodes(&e->bnodes, &e->bnodes_cap, (uint64_t)std::min(nk, FB) * pl.max_nodes, 2);
+  if (rc) return rc;
+  if (!e->d_gtmp) HIP_TRY(hipMalloc(&e->d_gtmp, (size_t)16 * e->cfg.record_bytes));
+  return PIR_OK;
 }
 
 // nk keys (raw, key_len apart) against one partition slice, one shard pass per group of G
@@ -456,45 +539,41 @@ int batch_group(const pir_engine* e) {
 //   aux: scan + reduce of group j (after its leaf stage)
 // so the leaf stage of group j+1 runs beside the scan of group j.  (Node-writing stages beside
 // a scan are starved of the CU's memory pipeline, hence the up-front upper stages.)
+// queue (answer_stream's shared queue, G keys per pass): the nk keys go into ceil(nk / G) groups
+// of as equal sizes as possible (20 keys at G = 8: 7 + 7 + 6, not 8 + 8 + 4: every group keeps the
+// full-width scan and its key-major packed leaf stores, and the leaf stages, which bound the
+// pipeline, are spread evenly; $PIR_STREAM_NARROW=1 instead gives a group of ng < G keys the
+// narrowest scan that holds it, the next power of two >= ng key slots -- measured slower,
+// profiles/stream_share/README.md); the last group's reduce runs on s after the join, and a
+// profiled queue stamps EV_SCAN_B before its first kernel and EV_SCAN_E after its last scan
+// (both on s)
 int answer_batch_core(pir_engine* e, const uint8_t* d_raw, int nk, int log_parts_total,
-                      uint64_t prefix, uint64_t row0, uint8_t* d_out, hipStream_t s) {
+                      uint64_t prefix, uint64_t row0, uint8_t* d_out, hipStream_t s, int G,
+                      bool queue) {
   const auto& c = e->cfg;
-  const int G = batch_group(e);
-  const int W = G * e->nrp;
   e->last_batch_group = G;
   e->last_fused = 0;
   e->last_chunks = 1;
-  const pir::TreePlan pl = pir::make_plan(c.log_num_records, log_parts_total, prefix, e->batch_k_last, c.num_parties, 8);
-  pir::ScanShape sh =
-      pir::make_scan_shape(pl.nleaves, e->pitch, W, e->num_cus, e->batch_scan_bpc);
-  const size_t cb_bytes = (size_t)pl.nleaves * W;
-  // k_scan_t reads the group's shares key-major (key g's nrp bytes of leaf i at g * nleaves *
-  // nrp + i * nrp), so each tree's leaf stage writes its shares contiguously (packed 16-byte
-  // stores); the other scans read them interleaved per record (cb[i][W], key g at g * nrp)
-  const bool kmaj = sh.tfold && !(getenv("PIR_BATCH_KMAJOR") && atoi(getenv("PIR_BATCH_KMAJOR")) == 0);
-  if (kmaj) {
-    sh.ckey = (uint32_t)e->nrp;
-    sh.ckoff = (uint64_t)pl.nleaves * e->nrp;
-  }
-  // super-group: as many keys as kBatchNodeBytes of upper-level nodes hold (a multiple of G)
-  const uint64_t per_key = 2 * pl.max_nodes * (sizeof(uint4) + sizeof(uint32_t));
-  int FB = (int)std::min<uint64_t>(kFrontBatch, std::max<uint64_t>(1, kBatchNodeBytes / per_key));
-  FB = std::max(G, FB / G * G);
-  const int nsg = std::min(nk, FB);
-  int rc = ensure_slabs(e, (size_t)sh.grid.x * sh.grid.y * sh.slab_bytes);
-  if (!rc) rc = ensure_buf(&e->d_cb, &e->cb_cap, 2 * cb_bytes);
-  if (!rc) rc = ensure_batch(e, nk);
-  if (!rc) rc = ensure_nodes(&e->bnodes, &e->bnodes_cap, (uint64_t)nsg * pl.max_nodes, 2);
-  if (rc) return rc;
-  if (!e->d_gtmp) HIP_TRY(hipMalloc(&e->d_gtmp, (size_t)16 * c.record_bytes));
+  int FB = G;
+  const pir::TreePlan pl = batch_plan(e, log_parts_total, prefix, G, &FB);
+  bool kmaj_full = false;
+  const pir::ScanShape sh_full = group_scan_shape(e, pl.nleaves, G, G, &kmaj_full);
+  const size_t cb_bytes = (size_t)pl.nleaves * G * e->nrp;
+  if (int rc = ensure_batched(e, pl, FB, nk, G, queue && e->stream_narrow)) return rc;
   const size_t out_bytes = (size_t)c.num_rounds * c.record_bytes;
   const int last = pl.nstages - 1;
+  hipEvent_t* ev = queue ? e->ev : nullptr;
+  if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
   HIP_TRY(hipEventRecord(e->ev_fork, s));
   HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-  for (int q0 = 0, j = 0; q0 < nk; q0 += G, ++j) {
-    const int ng = std::min(G, nk - q0), b = j & 1, r0 = q0 % FB;
-    if (r0 == 0) {  // frontier + upper stages of the next FB keys
+  const int ngroups = (nk + G - 1) / G;
+  for (int q0 = 0, j = 0, ng = 0, fb0 = 0, fb_end = 0; q0 < nk; q0 += ng, ++j) {
+    ng = queue && !e->stream_narrow ? nk / ngroups + (j < nk % ngroups ? 1 : 0) : std::min(G, nk - q0);
+    const int b = j & 1;
+    if (q0 + ng > fb_end) {  // frontier + upper stages of the next FB keys
       const int nf = std::min(FB, nk - q0);
+      fb0 = q0;
+      fb_end = q0 + nf;
       const pir::KeySrc ks{d_raw + (size_t)q0 * e->key_len, c.num_parties, c.log_num_records,
                            c.num_rounds, c.party_index - 1, e->d_keys + q0};
       HIP_TRY(pir::launch_frontier(pl, ks, e->bnodes, s, nf, (size_t)e->key_len, pl.max_nodes));
@@ -504,6 +583,15 @@ int answer_batch_core(pir_engine* e, const uint8_t* d_raw, int nk, int log_parts
                                    last, 0, &up));
       }
     }
+    // the group's key slots and their scan
+    const int r0 = q0 - fb0;
+    int gw = G;
+    if (queue && e->stream_narrow)
+      for (gw = 1; gw < ng;) gw *= 2;
+    bool kmaj = kmaj_full;
+    const pir::ScanShape sh = gw == G ? sh_full : group_scan_shape(e, pl.nleaves, gw, G, &kmaj);
+    const int W = gw * e->nrp;
+    const bool tail_on_s = queue && q0 + ng >= nk;
     uint8_t* cb = e->d_cb + b * cb_bytes;
     if (j >= 2) HIP_TRY(hipStreamWaitEvent(s, e->ev_cb_free[b], 0));
     // the leaf stage of the ng trees of the group side by side: grid row y = key q0 + y
@@ -520,17 +608,27 @@ int answer_batch_core(pir_engine* e, const uint8_t* d_raw, int nk, int log_parts
     HIP_TRY(pir::launch_scan(sh, e->d_shard + row0 * e->pitch, pl.nleaves, cb, e->d_slabs, false,
                              e->aux));
     HIP_TRY(hipEventRecord(e->ev_cb_free[b], e->aux));
+    hipStream_t rs = e->aux;
+    if (tail_on_s) {
+      HIP_TRY(hipEventRecord(e->ev_join, e->aux));
+      HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
+      if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_E], s));
+      rs = s;
+    }
     uint8_t* dst = d_out + (size_t)q0 * out_bytes;
-    if (e->nrp == c.num_rounds && ng == G) {
-      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, dst, e->aux));
+    if (e->nrp == c.num_rounds && ng == gw) {
+      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, dst, rs));
     } else {
-      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, e->d_gtmp, e->aux));
+      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, e->d_gtmp, rs));
       HIP_TRY(hipMemcpy2DAsync(dst, out_bytes, e->d_gtmp, (size_t)e->nrp * c.record_bytes,
-                               out_bytes, ng, hipMemcpyDeviceToDevice, e->aux));
+                               out_bytes, ng, hipMemcpyDeviceToDevice, rs));
     }
   }
-  HIP_TRY(hipEventRecord(e->ev_join, e->aux));
-  HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
+  if (!queue) {
+    HIP_TRY(hipEventRecord(e->ev_join, e->aux));
+    HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
+  }
+  if (ev) HIP_TRY(hipEventRecord(ev[EV_RED], s));
   return PIR_OK;
 }
 
@@ -605,66 +703,82 @@ constexpr int kNumQueryPhases = 6;
 
 // Mean per-phase device times over the answers recorded since the last read.  tree_leaves and
 // scan are the summed kernel durations of the C pipelined chunks (they overlap each other).
+// Every slot is read with the layout of its own answer (only events recorded in it); the
+// phases reported are those of the latest answer's path, a slot of the other layout adding to
+// the phases the two share (scan, reduce, comm_fold, total).  A shared queue reports k_query's
+// phases with fused = 0: "scan" = its first kernel -> the end of its last scan.
 int read_timings(pir_engine* e, pir_kernel_time* out, int max) {
-  const int n = std::min(max, kNumPhases);
   if (e->prof.empty() || e->prof_count == 0) return 0;
-  const int cnt = e->prof_count, sz = (int)e->prof.size(), C = e->last_chunks;
-  HIP_TRY(hipEventSynchronize(e->prof[(e->prof_next + sz - 1) % sz].ev[EV_END]));
-  double acc[kNumPhases] = {};
+  const int cnt = e->prof_count, sz = (int)e->prof.size();
+  const pir_engine::ProfSlot& newest = e->prof[(e->prof_next + sz - 1) % sz];
+  HIP_TRY(hipEventSynchronize(newest.ev[EV_END]));
+  auto five = [](const pir_engine::ProfSlot& sl) { return sl.queue || sl.fused == 2; };
+  // accumulators in kPhaseNames' order; "launch" (the five-event layout) beside them
+  double acc[kNumPhases] = {}, launch = 0;
   auto el = [](hipEvent_t a, hipEvent_t b, double& sum) -> hipError_t {
     float ms = 0;
     hipError_t r = hipEventElapsedTime(&ms, a, b);
     sum += ms;
     return r;
   };
-  if (e->last_fused == 2) {
-    const int nq = std::min(max, kNumQueryPhases);
-    for (int k = 0; k < cnt; ++k) {
-      const hipEvent_t* v = e->prof[(e->prof_next + sz - cnt + k) % sz].ev;
-      HIP_TRY(el(v[EV_START], v[EV_SCAN_B], acc[0]));
-      HIP_TRY(el(v[EV_SCAN_B], v[EV_SCAN_E], acc[1]));
-      HIP_TRY(el(v[EV_SCAN_E], v[EV_RED], acc[2]));
-      HIP_TRY(el(v[EV_RED], v[EV_END], acc[3]));
-      HIP_TRY(el(v[EV_START], v[EV_END], acc[4]));
-    }
-    acc[5] = 2.0 * cnt;
-    for (int i = 0; i < nq; ++i) {
-      snprintf(out[i].name, sizeof out[i].name, "%s", kQueryPhaseNames[i]);
-      out[i].ms = (float)(acc[i] / cnt);
-    }
-    e->prof_count = 0;
-    return nq;
-  }
   for (int k = 0; k < cnt; ++k) {
-    const hipEvent_t* v = e->prof[(e->prof_next + sz - cnt + k) % sz].ev;
-    HIP_TRY(el(v[EV_START], v[EV_KEY], acc[0]));
-    HIP_TRY(el(v[EV_KEY], v[EV_FRONT], acc[1]));
-    for (int j = 0; j < C; ++j) {
-      HIP_TRY(el(v[EV_LEAF_B + j], v[EV_LEAF_E + j], acc[2]));
-      HIP_TRY(el(v[EV_SCAN_B + j], v[EV_SCAN_E + j], acc[3]));
+    const pir_engine::ProfSlot& sl = e->prof[(e->prof_next + sz - cnt + k) % sz];
+    const hipEvent_t* v = sl.ev;
+    if (five(sl)) {
+      HIP_TRY(el(v[EV_START], v[EV_SCAN_B], launch));
+      HIP_TRY(el(v[EV_SCAN_B], v[EV_SCAN_E], acc[3]));
+      HIP_TRY(el(v[EV_SCAN_E], v[EV_RED], acc[4]));
+    } else {
+      HIP_TRY(el(v[EV_START], v[EV_KEY], acc[0]));
+      HIP_TRY(el(v[EV_KEY], v[EV_FRONT], acc[1]));
+      for (int j = 0; j < sl.chunks; ++j) {
+        HIP_TRY(el(v[EV_LEAF_B + j], v[EV_LEAF_E + j], acc[2]));
+        HIP_TRY(el(v[EV_SCAN_B + j], v[EV_SCAN_E + j], acc[3]));
+      }
+      HIP_TRY(el(v[EV_PRERED], v[EV_RED], acc[4]));
     }
-    HIP_TRY(el(v[EV_PRERED], v[EV_RED], acc[4]));
     HIP_TRY(el(v[EV_RED], v[EV_END], acc[5]));
     HIP_TRY(el(v[EV_START], v[EV_END], acc[6]));
+    acc[7] += sl.chunks;
+    acc[8] += sl.fused;
   }
-  acc[7] = C * cnt;
-  acc[8] = e->last_fused * cnt;
+  e->prof_count = 0;
+  if (five(newest)) {
+    const int nq = std::min(max, kNumQueryPhases);
+    const double q[kNumQueryPhases] = {launch, acc[3], acc[4], acc[5], acc[6], acc[8]};
+    for (int i = 0; i < nq; ++i) {
+      snprintf(out[i].name, sizeof out[i].name, "%s", kQueryPhaseNames[i]);
+      out[i].ms = (float)(q[i] / cnt);
+    }
+    return nq;
+  }
+  const int n = std::min(max, kNumPhases);
   for (int i = 0; i < n; ++i) {
     snprintf(out[i].name, sizeof out[i].name, "%s", kPhaseNames[i]);
     out[i].ms = (float)(acc[i] / cnt);
   }
-  e->prof_count = 0;
   return n;
+}
+
+// the next profiling slot, labelled with the path whose events it will hold
+hipEvent_t* prof_slot(pir_engine* e, int fused, int chunks, bool queue) {
+  pir_engine::ProfSlot& sl = e->prof[e->prof_next];
+  sl.fused = fused;
+  sl.chunks = chunks;
+  sl.queue = queue;
+  e->prof_next = (e->prof_next + 1) % (int)e->prof.size();
+  e->prof_count = std::min(e->prof_count + 1, (int)e->prof.size());
+  return sl.ev;
 }
 
 int answer_dev_locked(pir_engine* e, const uint8_t* d_key, uint8_t* d_result, hipStream_t s) {
   const auto& c = e->cfg;
   const size_t out_bytes = (size_t)c.num_rounds * c.record_bytes;
   e->ev = nullptr;
+  pir_engine::ProfSlot* slot = nullptr;
   if (!e->prof.empty()) {
-    e->ev = e->prof[e->prof_next].ev;
-    e->prof_next = (e->prof_next + 1) % (int)e->prof.size();
-    e->prof_count = std::min(e->prof_count + 1, (int)e->prof.size());
+    slot = &e->prof[e->prof_next];
+    e->ev = prof_slot(e, 0, 1, false);
   }
   hipEvent_t* ev = e->ev;
   if (ev) HIP_TRY(hipEventRecord(ev[EV_START], s));
@@ -681,6 +795,10 @@ int answer_dev_locked(pir_engine* e, const uint8_t* d_key, uint8_t* d_result, hi
   int rc = answer_core(e, d_key, c.log_num_partitions, (uint64_t)c.partition_index, 0,
                        part_out, s);
   if (rc) return rc;
+  if (slot) {  // the path answer_core took: which events the slot holds
+    slot->fused = e->last_fused;
+    slot->chunks = e->last_chunks;
+  }
   if (e->comm) {
     if (int rc = exchange(e, e->d_part, out_bytes, e->d_gather, d_result, s)) return rc;
   }
@@ -715,7 +833,7 @@ int answer_batch_locked(pir_engine* e, const uint8_t* d_keys, int nk, uint8_t* d
     part_out = e->d_bpart;
   }
   int rc = answer_batch_core(e, d_keys, nk, c.log_num_partitions, (uint64_t)c.partition_index, 0,
-                             part_out, s);
+                             part_out, s, batch_group(e), false);
   if (rc) return rc;
   if (e->comm) {
     if (int rc = exchange(e, e->d_bpart, total, e->d_bgather, d_result, s)) return rc;
@@ -723,9 +841,12 @@ int answer_batch_locked(pir_engine* e, const uint8_t* d_keys, int nk, uint8_t* d
   return PIR_OK;
 }
 
-// nk independent queries, each its own tree and full shard pass, answered back to back: one
-// k_query launch when the shape allows (the tree of query k+1 overlaps the scan of query k),
-// else one answer after another.  d_result: nk x nq x efs.
+// nk independent queries (each its own key and tree) handed over at once.  Where stream_group
+// gives a group size, G queued keys share each pass over the shard (answer_batch_core's leaf
+// stage -> share buffer -> one scan of G * nrp rounds; no answer is due before the queue's
+// last reduce, so none comes later than with a pass each).  Otherwise every query has its own
+// full shard pass: one k_query launch when the shape allows (the tree of query k+1 overlaps
+// the scan of query k), else one answer after another.  d_result: nk x nq x efs.
 int answer_stream_locked(pir_engine* e, const uint8_t* d_keys, int nk, uint8_t* d_result,
                          hipStream_t s) {
   const auto& c = e->cfg;
@@ -735,7 +856,8 @@ int answer_stream_locked(pir_engine* e, const uint8_t* d_keys, int nk, uint8_t* 
   const pir::QueryPlan qp = pir::make_query_plan(c.log_num_records, c.log_num_partitions,
                                                  c.num_parties, c.num_rounds, e->pitch, e->num_cus,
                                                  nk);
-  if (c.is_byzantine || !qp.tile || !e->allow_query || !e->allow_fused) {
+  const int G = stream_group(e, nk);
+  if (!G && (c.is_byzantine || !qp.tile || !e->allow_query || !e->allow_fused)) {
     for (int k = 0; k < nk; ++k) {
       int rc = answer_dev_locked(e, d_keys + (size_t)k * e->key_len, d_result + k * out_bytes, s);
       if (rc) return rc;
@@ -751,13 +873,13 @@ int answer_stream_locked(pir_engine* e, const uint8_t* d_keys, int nk, uint8_t* 
     part_out = e->d_bpart;
   }
   if (!e->prof.empty()) {  // one event set for the whole queue (phases of the one launch)
-    e->ev = e->prof[e->prof_next].ev;
-    e->prof_next = (e->prof_next + 1) % (int)e->prof.size();
-    e->prof_count = std::min(e->prof_count + 1, (int)e->prof.size());
+    e->ev = prof_slot(e, G ? 0 : 2, 1, true);
     HIP_TRY(hipEventRecord(e->ev[EV_START], s));
   }
-  int rc = answer_query(e, qp, d_keys, nk, c.log_num_partitions, (uint64_t)c.partition_index, 0,
-                        part_out, s);
+  int rc = G ? answer_batch_core(e, d_keys, nk, c.log_num_partitions,
+                                 (uint64_t)c.partition_index, 0, part_out, s, G, true)
+             : answer_query(e, qp, d_keys, nk, c.log_num_partitions,
+                            (uint64_t)c.partition_index, 0, part_out, s);
   if (rc) return rc;
   if (e->comm) {
     if (int rc = exchange(e, e->d_bpart, total, e->d_bgather, d_result, s)) return rc;
@@ -1041,6 +1163,13 @@ int pir_engine_create(const pir_engine_config* cfg, pir_engine_t** out) {
     if (bg) e->batch_group = atoi(bg);
     const char* bb = getenv("PIR_BATCH_SCAN_BPC");
     if (bb) e->batch_scan_bpc = std::max(1, atoi(bb));
+    // $PIR_STREAM_SHARE / $PIR_STREAM_G: queued keys per shard pass (stream_group)
+    const char* ss = getenv("PIR_STREAM_SHARE");
+    if (ss && ss[0]) e->stream_share = std::max(0, std::min(2, atoi(ss)));
+    const char* sg = getenv("PIR_STREAM_G");
+    if (sg) e->stream_group = std::max(0, std::min(16, atoi(sg)));
+    const char* sn = getenv("PIR_STREAM_NARROW");
+    e->stream_narrow = sn && atoi(sn) == 1;
     const char* bk = getenv("PIR_BATCH_KLAST");
     if (bk) e->batch_k_last = std::max(1, std::min(12, atoi(bk)));
     const int tile = pir::fused_tile(c.num_rounds, e->pitch, e->rows, e->num_cus);
@@ -1585,8 +1714,22 @@ int pir_engine_reserve_queue(pir_engine_t* e, int num_keys) {
   const pir::QueryPlan qp = pir::make_query_plan(c.log_num_records, c.log_num_partitions,
                                                  c.num_parties, c.num_rounds, e->pitch, e->num_cus,
                                                  num_keys);
+  int rc = PIR_OK;
+  if (const int G = stream_group(e, num_keys)) {  // a shared queue: the batched path's buffers
+    int FB = G;
+    const pir::TreePlan pl = batch_plan(e, c.log_num_partitions, (uint64_t)c.partition_index, G, &FB);
+    rc = ensure_batched(e, pl, FB, num_keys, G, e->stream_narrow);
+    if (!rc && e->comm) {
+      const size_t total = (size_t)num_keys * c.num_rounds * c.record_bytes;
+      rc = ensure_buf(&e->d_bpart, &e->bpart_cap, total);
+      if (!rc) rc = ensure_buf(&e->d_bgather, &e->bgather_cap, total * e->nranks);
+    }
+    if (rc) return rc;
+  }
   if (!qp.tile) return PIR_OK;  // shapes k_query does not take allocate per answer
-  int rc = ensure_slabs(e, (size_t)num_keys * pir::query_slab_bytes(qp));
+  // k_query's own (a queue of one, or a shorter queue the policy leaves to it): the slabs
+  // only ever grow
+  rc = ensure_slabs(e, (size_t)num_keys * pir::query_slab_bytes(qp));
   if (!rc) rc = ensure_buf(&e->d_qscratch, &e->qscratch_cap, pir::query_scratch_bytes(qp));
   if (!rc && e->fused_reduce) rc = ensure_qcnt(e, num_keys * 8, e->stream);
   if (!rc && num_keys == 1) {  // the stealing buffer (this advances the generation once: harmless)

@@ -136,7 +136,9 @@ constexpr int kScanTThreads = PIR_SCAN_T_THREADS;
 constexpr int kScanTWavesPerEU = PIR_SCAN_T_WPE;
 constexpr int kScanTBlocksPerCU = kScanTWavesPerEU * 4 * 64 / kScanTThreads;
 bool scan_t_enabled();
-bool scan_t_shape(int nq, int nrp, uint32_t pitch);
+// prefer: also 4-5 rounds of wider records (a batched group's key-major shares: packed leaf
+// stores, which the interleaved layout of the k_scan_uni forms does not allow)
+bool scan_t_shape(int nq, int nrp, uint32_t pitch, bool prefer = false);
 hipError_t launch_scan_t(const ScanShape& sh, const uint8_t* d_shard, uint64_t nrec,
                          const uint8_t* d_c, uint8_t* d_slabs, int acc, hipStream_t s);
 // k_scan_uni for 4-5 rounds at two dwords per lane: four-Russians folds need 168 VGPRs, so one
@@ -144,7 +146,8 @@ hipError_t launch_scan_t(const ScanShape& sh, const uint8_t* d_shard, uint64_t n
 constexpr int kScanM4rThreads = 768;
 // blocks_per_cu <= 0: kScanBlocksPerCU.  One block per CU leaves room on every CU for a
 // 1024-thread tree workgroup beside the scan (batched answers overlap the two).
-ScanShape make_scan_shape(uint64_t nrec, uint32_t pitch, int nq, int num_cus, int blocks_per_cu = 0);
+ScanShape make_scan_shape(uint64_t nrec, uint32_t pitch, int nq, int num_cus, int blocks_per_cu = 0,
+                          bool prefer_t = false);
 // accumulate: XOR into the slabs instead of overwriting them (chunked scans of one answer)
 hipError_t launch_scan(const ScanShape& sh, const uint8_t* d_shard, uint64_t nrec,
                        const uint8_t* d_c, uint8_t* d_slabs, bool accumulate, hipStream_t s);

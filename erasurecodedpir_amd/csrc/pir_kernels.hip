@@ -3308,7 +3308,8 @@ int final_stage_blocks(const TreePlan& pl) {
 
 static int vec_for(int nq) { return nq <= 3 ? 4 : (nq <= 8 ? 2 : 1); }
 
-ScanShape make_scan_shape(uint64_t nrec, uint32_t pitch, int nq, int num_cus, int blocks_per_cu) {
+ScanShape make_scan_shape(uint64_t nrec, uint32_t pitch, int nq, int num_cus, int blocks_per_cu,
+                          bool prefer_t) {
   ScanShape sh{};
   sh.nq = nq;
   sh.nrp = nq == 1 ? 1 : (nq == 2 ? 2 : (nq <= 4 ? 4 : (nq <= 8 ? 8 : 16)));
@@ -3323,7 +3324,7 @@ ScanShape make_scan_shape(uint64_t nrec, uint32_t pitch, int nq, int num_cus, in
   else if (nq == 3 && sh.vec == 4 && pitch / 8 < (uint32_t)kColGroupLanes &&
            pitch / 4 >= (uint32_t)kColGroupLanes)
     sh.vec = 1;  // 3 rounds, 256-511 B: a record per wave row at VEC = 1
-  sh.tfold = scan_t_shape(nq, sh.nrp, pitch);
+  sh.tfold = scan_t_shape(nq, sh.nrp, pitch, prefer_t);
   if (sh.tfold) sh.vec = 1;  // the transposed fold: one dword per lane, any record width
   sh.pitch = pitch;
   sh.cpr = pitch / (sh.vec * 4);

@@ -244,10 +244,10 @@ bool scan_t_enabled() { return scan_t_mode() != 0; }
 // 8); 4-5 rounds only for records narrower than a VEC = 2 wave row (the 768-thread GPR-index
 // k_scan_uni at two dwords per lane is faster there: Hollanti 5 rounds at 1 KiB 4.53 against
 // 4.91 ms, profiles/r03_bench_ch5_*.json)
-bool scan_t_shape(int nq, int nrp, uint32_t pitch) {
+bool scan_t_shape(int nq, int nrp, uint32_t pitch, bool prefer) {
   if (!scan_t_enabled() || nq < 4 || nq > 8 || nq > nrp || (nrp != 4 && nrp != 8)) return false;
   if (pitch % 4 != 0 || pitch / 4 < (uint32_t)kColGroupLanes) return false;
-  return nq >= 6 || pitch / 8 < (uint32_t)kColGroupLanes || scan_t_mode() == 2;
+  return nq >= 6 || pitch / 8 < (uint32_t)kColGroupLanes || prefer || scan_t_mode() == 2;
 }
 
 template <int NQ, int NRP>

@@ -295,8 +295,10 @@ class Engine:
               "answer_batch_dev")
 
     def answer_stream_dev(self, d_keys, num_keys, d_result, stream=None):
-        """A queue of independent queries, each its own tree and full shard pass, answered
-        back to back in one launch (device pointers; asynchronous)."""
+        """A queue of independent queries (device pointers; asynchronous): each its own key and
+        tree and the answer answer_dev would give.  Where it measured faster the queued keys
+        share passes over the shard (8 keys per read of it; $PIR_STREAM_SHARE, $PIR_STREAM_G:
+        include/pir_engine.h), else each has its own full pass, back to back in one launch."""
         check(self._lib.pir_engine_answer_stream_dev(self._h, d_keys, num_keys, d_result, stream),
               "answer_stream_dev")
 

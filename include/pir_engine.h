@@ -200,13 +200,21 @@ int pir_engine_answer_batch_dev(pir_engine_t *e, const uint8_t *d_keys, int num_
 int pir_engine_answer_batch(pir_engine_t *e, const uint8_t *keys, int num_keys,
                             uint8_t *results);
 /* a queue of `num_keys` independent queries (keys of key_len bytes back to back; results
- * num_keys x num_rounds x record_bytes), each answered exactly as pir_engine_answer_dev would
- * -- its own DPF tree and its own full pass over the shard -- back to back in one launch where
- * the shape allows, so that the tree of query k+1 is built while query k's rows stream. */
+ * num_keys x num_rounds x record_bytes), each with its own DPF key and tree and the answer
+ * pir_engine_answer_dev would give, byte for byte.  The queue is handed over whole and nothing
+ * is returned before its end, so on shapes where that measured faster (one round, records of
+ * 256 B - 1 KiB, >= 2^20 rows, >= 4 keys) the queued keys share passes over the shard: 8 keys
+ * per read of it, as pir_engine_answer_batch_dev does.  Elsewhere every query has its own full
+ * pass, back to back in one k_query launch where the shape allows (the tree of query k+1 built
+ * while query k's rows stream).  $PIR_STREAM_SHARE, read at engine creation: 0 never shares,
+ * unset or 1 follows that policy, 2 shares on every shape the batched path takes;
+ * $PIR_STREAM_G overrides the keys per pass ($PIR_BATCH_G steers answer_batch only). */
 int pir_engine_answer_stream_dev(pir_engine_t *e, const uint8_t *d_keys, int num_keys,
                                  uint8_t *d_result, void *stream);
 /* pre-size the device work buffers of pir_engine_answer_stream_dev for queues of up to
- * `num_keys` queries (a server sizes its queue at setup), so that no answer call allocates:
+ * `num_keys` queries (a server sizes its queue at setup), so that no answer call allocates
+ * (k_query's slabs and scratch; for a shared queue the batch scan's slabs, both share buffers,
+ * the batched node buffers, the parsed keys and, with a communicator, the partition buffers):
  * the reference has no counterpart (its buffers are host mallocs per call, server.cpp:108-114). */
 int pir_engine_reserve_queue(pir_engine_t *e, int num_keys);
 /* keys per shard pass: 0 = automatic (8 / nrp), else a power of two <= 16 / nrp, where nrp =
@@ -223,9 +231,13 @@ int pir_engine_memcpy_h2d(pir_engine_t *e, void *d_dst, const void *h_src, size_
 int pir_engine_memcpy_d2h(pir_engine_t *e, void *h_dst, const void *d_src, size_t bytes);
 
 /* ---- per-phase device time of answers (HIP events on the answering stream) ---- */
-/* phases: key_prep, tree_frontier, tree_leaves, scan, reduce, comm_fold.  `slots` event sets
- * are kept in a ring (0 = off); last_timings averages the answers recorded since the previous
- * read (at most `slots`), fills up to `max` {name, ms} pairs and returns the count. */
+/* phases: key_prep, tree_frontier, tree_leaves, scan, reduce, comm_fold, total, chunks, fused;
+ * an answer in k_query (fused = 2) and a shared queue (fused = 0) have launch, scan, reduce,
+ * comm_fold, total, fused, a shared queue's scan being its first kernel -> the end of its last
+ * scan.  `slots` event sets are kept in a ring (0 = off), each remembering its answer's path;
+ * last_timings averages the answers recorded since the previous read (at most `slots`), every
+ * slot read by its own path and reported under the newest answer's phase names, fills up to
+ * `max` {name, ms} pairs and returns the count. */
 typedef struct {
     char name[32];
     float ms;
