@@ -99,6 +99,11 @@ PROTOTYPES = {
     "pir_engine_eval_all": (_I, [_P, _P, _P]),
     "pir_engine_answer_coefs": (_I, [_P, ctypes.POINTER(_P), _U64, _U64, _P]),
     "pir_engine_answer_coefs_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
+    "pir_engine_shamir_response_len": (_U64, [_I, _U32]),
+    "pir_engine_answer_shamir": (_I, [_P, ctypes.POINTER(_P), _U64, _U64, _P]),
+    "pir_engine_answer_shamir_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
+    "pir_engine_encode_hermite_dev": (_I, [_P, _P, _U64, _U64, _U32, _I, _I]),
+    "pir_engine_encode_hermite_rows": (_I, [_P, _P, _U64, _U32, _I, _I]),
     "pir_engine_answer_mp": (_I, [_P, _P, _U64, _I, _I, _I, _I, _P]),
     "pir_engine_answer_mp_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "pir_engine_mp_num_keys": (_I, [_I, _I]),
@@ -207,6 +212,9 @@ PROTOTYPES = {
     "genWoodruffVs": (None, [_I, _I, _P]),
     "genWoodruffQuery": (None, [U128, _I, _I, _I, _P, _P]),
     "assembleWoodruffResponses": (None, [ctypes.POINTER(CClient), _P, _P, _P, _P]),
+    "pirEnableShamirMode": (None, [_I]),
+    "runOptShamirDPFQuery": (None, [ctypes.POINTER(CServer), ctypes.POINTER(c_u8_p),
+                                    ctypes.POINTER(c_u8_p)]),
     "pirSetDevice": (None, [_I]),
     "pirServerShardChanged": (None, [ctypes.POINTER(CServer)]),
     "pirServerSyncRows": (None, [ctypes.POINTER(CServer)]),

@@ -23,4 +23,11 @@ hipError_t launch_encode_within(const uint8_t* d_files, uint64_t file_pitch, uin
                                 uint64_t rows, uint64_t row0, uint32_t pitch, uint32_t efs,
                                 hipStream_t s);
 
+// The Shamir mode's derivative ("Hermite") rows (client.cpp:57-68, 103-107): row r = XOR over odd
+// j, 1 <= j < k, of gf_pow(party, j - 1) * part j of file r; otherwise as launch_encode_within.
+hipError_t launch_encode_hermite(const uint8_t* d_files, uint64_t file_pitch, uint64_t num_files,
+                                 uint32_t file_bytes, int k, int party, uint8_t* d_shard,
+                                 uint64_t rows, uint64_t row0, uint32_t pitch, uint32_t efs,
+                                 hipStream_t s);
+
 }  // namespace pir

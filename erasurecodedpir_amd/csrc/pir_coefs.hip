@@ -118,30 +118,55 @@ __global__ __launch_bounds__(256) void k_encode_within(
   }
 }
 
-hipError_t launch_encode_within(const uint8_t* d_files, uint64_t file_pitch, uint64_t num_files,
-                                uint32_t file_bytes, int k, int party, uint8_t* d_shard,
-                                uint64_t rows, uint64_t row0, uint32_t pitch, uint32_t efs,
-                                hipStream_t s) {
-  if (k < 1 || k > 16 || pitch % 16 != 0 || efs > pitch) return hipErrorInvalidValue;
-  WithinCoefs co{};
-  for (int j = 0; j < k; ++j) {  // gf_pow(party, j) (coding.cpp:46-60; pow(0, e) == 1)
-    uint32_t r = 1;
-    for (int t = 0; t < j && party; ++t) {
-      uint32_t a = r, b = (uint32_t)party, m = 0;
-      while (b) {
-        if (b & 1) m ^= a;
-        a = ((a << 1) ^ ((a & 0x80) ? 0x11d : 0)) & 0xff;
-        b >>= 1;
-      }
-      r = m;
+// gf_pow(party, j) (coding.cpp:46-60; pow(0, e) == 1)
+static uint8_t gf_pow_h(int party, int j) {
+  uint32_t r = 1;
+  for (int t = 0; t < j && party; ++t) {
+    uint32_t a = r, b = (uint32_t)party, m = 0;
+    while (b) {
+      if (b & 1) m ^= a;
+      a = ((a << 1) ^ ((a & 0x80) ? 0x11d : 0)) & 0xff;
+      b >>= 1;
     }
-    co.c[j] = (uint8_t)r;
+    r = m;
   }
+  return (uint8_t)r;
+}
+
+static hipError_t launch_encode_parts(const WithinCoefs& co, const uint8_t* d_files,
+                                      uint64_t file_pitch, uint64_t num_files,
+                                      uint32_t file_bytes, int k, uint8_t* d_shard, uint64_t rows,
+                                      uint64_t row0, uint32_t pitch, uint32_t efs, hipStream_t s) {
+  if (k < 1 || k > 16 || pitch % 16 != 0 || efs > pitch) return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;
   const uint64_t total = rows * (pitch / 16);
   const dim3 grid((unsigned)std::min<uint64_t>((total + 255) / 256, 1u << 16));
   hipLaunchKernelGGL(k_encode_within, grid, dim3(256), 0, s, d_files, file_pitch, num_files,
                      file_bytes, k, co, d_shard, rows, row0, pitch, efs);
   return hipGetLastError();
+}
+
+hipError_t launch_encode_within(const uint8_t* d_files, uint64_t file_pitch, uint64_t num_files,
+                                uint32_t file_bytes, int k, int party, uint8_t* d_shard,
+                                uint64_t rows, uint64_t row0, uint32_t pitch, uint32_t efs,
+                                hipStream_t s) {
+  WithinCoefs co{};
+  for (int j = 0; j < k && j < 16; ++j) co.c[j] = gf_pow_h(party, j);
+  return launch_encode_parts(co, d_files, file_pitch, num_files, file_bytes, k, d_shard, rows,
+                             row0, pitch, efs, s);
+}
+
+// The formal derivative of the within-file polynomial sum_j part_j x^j at x = party: over
+// GF(2^8) only the odd j survive, with coefficient gf_pow(party, j - 1).  The same kernel as
+// the value rows with that coefficient vector (a zero coefficient adds nothing).
+hipError_t launch_encode_hermite(const uint8_t* d_files, uint64_t file_pitch, uint64_t num_files,
+                                 uint32_t file_bytes, int k, int party, uint8_t* d_shard,
+                                 uint64_t rows, uint64_t row0, uint32_t pitch, uint32_t efs,
+                                 hipStream_t s) {
+  WithinCoefs co{};
+  for (int j = 1; j < k && j < 16; j += 2) co.c[j] = gf_pow_h(party, j - 1);
+  return launch_encode_parts(co, d_files, file_pitch, num_files, file_bytes, k, d_shard, rows,
+                             row0, pitch, efs, s);
 }
 
 }  // namespace pir

@@ -7,6 +7,13 @@
 //                            here computed on the GPU by pir_engine_encode_across_dev)
 //   TREE_SEARCH_REQUEST (1)  TreeSearchRequest{Key} -> TreeSearchResponse{Results, PartyIndex,
 //                            ServerLatency, ReceiveTime, SendTime}   (tree.go:17-101)
+//   SHAMIR_SEARCH_REQUEST (2)  ShamirSearchRequest{Key [][]byte} -> ShamirSearchResponse{Results,
+//                            ServerLatency, ReceiveTime, SendTime}  (shamir.go:16-130, Mode 2:
+//                            NUM_ROUNDS keys of calcShamirDPFKeyLength bytes; the value and
+//                            Hermite rows are encoded within files on the GPU and scanned there;
+//                            Results = NUM_ROUNDS x calcShamirResponseLength bytes -- the XOR of
+//                            the reference's Thread slices, which are honest for a Byzantine
+//                            server too)
 //   MULTIPARTY_SEARCH_REQUEST (3)  MultipartySearchRequest{Key} -> MultipartySearchResponse{
 //                            Results, ServerLatency, ReceiveTime, SendTime}  (multiparty.go:16-103,
 //                            Mode 1: shares of the sqrt(N) DPF key scanned on the GPU)
@@ -57,7 +64,8 @@
 namespace {
 
 enum : uint8_t {  // common.go:147-154
-  SETUP_REQUEST = 0, TREE_SEARCH_REQUEST = 1, MULTIPARTY_SEARCH_REQUEST = 3,
+  SETUP_REQUEST = 0, TREE_SEARCH_REQUEST = 1, SHAMIR_SEARCH_REQUEST = 2,
+  MULTIPARTY_SEARCH_REQUEST = 3,
   HOLLANTI_SEARCH_REQUEST = 4, CD732_SEARCH_REQUEST = 5, TEST_REQUEST = 7
 };
 
@@ -252,9 +260,10 @@ struct Server {
   std::mutex mu;
   pir_engine_t* eng = nullptr;
   // of the current engine (the params globals may move on): mode, answer rows, record bytes,
-  // tree key length, multiparty (p, t), NUM_CD_KEYS_NEEDED, Hollanti coefficient-vector length
+  // tree key length, multiparty (p, t), NUM_CD_KEYS_NEEDED, Hollanti coefficient-vector length,
+  // Shamir key length and bytes per response row (efs elsewhere)
   int mode = -1, nq = 0, efs = 0, key_len = 0, p = 0, t = 0, cd_needed = 0;
-  uint64_t num_files = 0;
+  uint64_t num_files = 0, shamir_key_len = 0, row_len = 0;
 };
 Server g;
 
@@ -263,9 +272,9 @@ std::string setup(const MVal& req) {  // server.go:295-331
   const int t = (int)req.get_int("T", 1), k = (int)req.get_int("K", 1), r = (int)req.get_int("R");
   const int b = (int)req.get_int("B"), rho = (int)req.get_int("Rho", 1);
   const int mode = (int)req.get_int("Mode"), mac = (int)req.get_int("CheckMAC");
-  if (mode != 0 && mode != 1 && mode != 3 && mode != 4)
-    return "only the tree (0), multiparty (1), Hollanti (3) and covering-design (4) modes are "
-           "served by this engine";
+  if (mode < 0 || mode > 4)
+    return "only the tree (0), multiparty (1), Shamir (2), Hollanti (3) and covering-design (4) "
+           "modes are served by this engine";
   if (mac != 0) return "CheckMAC setups are outside this engine's scope";
   if (mode == 0 && (t != 1 || b != 0)) return "tree mode needs T = 1 and B = 0";
   if (mode == 1 && t < 1) return "multiparty mode needs T >= 1";
@@ -288,12 +297,15 @@ std::string setup(const MVal& req) {  // server.go:295-331
   // the party count only sizes tree-DPF keys (modes 1, 3 and 4 answer other key forms); the
   // party index also selects the encode-across evaluation point gf_pow(party, j) (client.cpp:
   // 84-89), so the encode-across modes keep the server's own (Hollanti passes it explicitly)
-  c.num_parties = mode == 3 ? 2 : (NUM_PARTIES < 2 ? 2 : NUM_PARTIES);
-  c.party_index = mode == 3 ? 1 : g.party;
-  c.log_num_records = LOG_NUM_ENCODED_FILES;
+  const bool within = mode == 2 || mode == 3;
+  c.num_parties = within ? 2 : (NUM_PARTIES < 2 ? 2 : NUM_PARTIES);
+  c.party_index = within ? 1 : g.party;
+  // Shamir: the Hermite rows behind the value rows (pir_engine_answer_shamir)
+  c.log_num_records = LOG_NUM_ENCODED_FILES + (mode == 2 ? 1 : 0);
   c.record_bytes = (uint32_t)ENCODED_FILE_SIZE_BYTES;
   c.num_rounds = rounds;
-  c.is_byzantine = g.byzantine || (int)req.get_int("IsByzantine");
+  // Shamir answers are the Thread slices of shamir.go:88-104: honest either way
+  c.is_byzantine = mode == 2 ? 0 : (g.byzantine || (int)req.get_int("IsByzantine"));
   if (pir_engine_create(&c, &g.eng) != PIR_OK) return std::string("engine: ") + pir_engine_last_error();
   if (ENCODE_ACROSS) {
     // the synthetic database of client.cpp:16-33, encoded across files on the GPU
@@ -305,6 +317,10 @@ std::string setup(const MVal& req) {  // server.go:295-331
     if (pir_engine_encode_within_dev(g.eng, nullptr, 0, (uint64_t)NUM_FILES, FILE_SIZE_BYTES, K,
                                      g.party) != PIR_OK)
       return std::string("encode: ") + pir_engine_last_error();
+    // and the derivative rows of client.cpp:57-68, 103-107 behind them
+    if (mode == 2 && pir_engine_encode_hermite_dev(g.eng, nullptr, 0, (uint64_t)NUM_FILES,
+                                                   FILE_SIZE_BYTES, K, g.party) != PIR_OK)
+      return std::string("encode: ") + pir_engine_last_error();
   }
   g.mode = mode;
   g.nq = rounds;
@@ -313,12 +329,15 @@ std::string setup(const MVal& req) {  // server.go:295-331
   g.t = T;
   g.cd_needed = NUM_CD_KEYS_NEEDED;
   g.num_files = (uint64_t)NUM_FILES;
+  g.shamir_key_len = mode == 2 ? (uint64_t)calcShamirDPFKeyLength(LOG_NUM_ENCODED_FILES) : 0;
+  g.row_len = mode == 2 ? pir_engine_shamir_response_len(LOG_NUM_ENCODED_FILES, (uint32_t)g.efs)
+                        : (uint64_t)g.efs;
   g.key_len = pir_engine_key_len(c.num_parties, c.log_num_records, c.num_rounds);
   return "";
 }
 
 // msgpack(error) then the search response map: Results [+ PartyIndex], the times
-void write_search(Writer& w, const std::string& err, int nq, int efs, const std::vector<uint8_t>& out,
+void write_search(Writer& w, const std::string& err, int nq, size_t efs, const std::vector<uint8_t>& out,
                   bool party_index, std::chrono::steady_clock::time_point t0,
                   std::chrono::system_clock::time_point recv) {
   err.empty() ? w.nil() : w.str(err);
@@ -326,7 +345,7 @@ void write_search(Writer& w, const std::string& err, int nq, int efs, const std:
   w.str("Results");
   if (err.empty()) {
     w.array((size_t)nq);
-    for (int a = 0; a < nq; ++a) w.bin(out.data() + (size_t)a * efs, (size_t)efs);
+    for (int a = 0; a < nq; ++a) w.bin(out.data() + (size_t)a * efs, efs);
   } else {
     w.array(0);
   }
@@ -363,19 +382,22 @@ void handle(SSL* ssl) {
       w.integer(std::chrono::duration_cast<std::chrono::nanoseconds>(
                     std::chrono::steady_clock::now() - t0).count());
     } else if (type == TREE_SEARCH_REQUEST || type == MULTIPARTY_SEARCH_REQUEST ||
-               type == HOLLANTI_SEARCH_REQUEST || type == CD732_SEARCH_REQUEST) {
-      // tree.go:17-101, multiparty.go, hollanti.go, cd732.go
+               type == HOLLANTI_SEARCH_REQUEST || type == CD732_SEARCH_REQUEST ||
+               type == SHAMIR_SEARCH_REQUEST) {
+      // tree.go:17-101, multiparty.go, hollanti.go, cd732.go, shamir.go
       const MVal* key = req.get("Key");
       std::vector<uint8_t> out;
-      int nq = 0, efs = 0;  // this answer's shape, read under the lock with the engine
+      int nq = 0;  // this answer's shape, read under the lock with the engine
+      size_t efs = 0;  // bytes per Results row
       {
         std::lock_guard<std::mutex> lk(g.mu);
         nq = g.nq;
-        efs = g.efs;
+        efs = (size_t)g.row_len;
         out.resize((size_t)nq * efs);
         const int want = type == TREE_SEARCH_REQUEST ? 0
                          : type == MULTIPARTY_SEARCH_REQUEST ? 1
-                         : type == CD732_SEARCH_REQUEST ? 4 : 3;
+                         : type == CD732_SEARCH_REQUEST ? 4
+                         : type == SHAMIR_SEARCH_REQUEST ? 2 : 3;
         int rc = PIR_OK;
         if (!g.eng) {
           err = "query before setup";
@@ -398,6 +420,16 @@ void handle(SSL* ssl) {
           else
             rc = pir_engine_answer_cd(g.eng, (const uint8_t*)key->s.data(), key->s.size(),
                                       g.cd_needed, nq, 0, 1, out.data());
+        } else if (type == SHAMIR_SEARCH_REQUEST) {  // Key [][]byte: NUM_ROUNDS keys of 2^x + 2^y bytes
+          std::vector<const uint8_t*> ptrs;
+          if (key && key->kind == MVal::ARR && (int)key->a.size() == nq)
+            for (const MVal& v : key->a)
+              if (is_bytes(&v) && v.s.size() == g.shamir_key_len)
+                ptrs.push_back((const uint8_t*)v.s.data());
+          if ((int)ptrs.size() != nq)
+            err = "bad key";
+          else
+            rc = pir_engine_answer_shamir(g.eng, ptrs.data(), 0, g.num_files, out.data());
         } else {  // Key [][]byte: NUM_ROUNDS coefficient vectors of NUM_FILES bytes
           std::vector<const uint8_t*> ptrs;
           if (key && key->kind == MVal::ARR && (int)key->a.size() == nq)
@@ -480,6 +512,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: pir_serve --port P --party I [--cert C --key K] [--device D]\n");
     return 2;
   }
+  pirEnableShamirMode(1);  // SETUP Mode 2 is served (a plain shim process refuses it)
   signal(SIGPIPE, SIG_IGN);
   SSL_CTX* ctx = make_ctx(cert, key);
   if (!ctx) {

@@ -27,6 +27,7 @@
 
 #include "../../include/pir_client.h"
 #include "../../include/pir_engine.h"
+#include "pir_server_internal.h"
 
 extern "C" {
 int NUM_PARTIES = 0;
@@ -62,6 +63,7 @@ int WOODRUFF_DERIVATIVE = 0;
 namespace {
 
 int g_device = -1;
+int g_shamir_mode = 0;  // pirEnableShamirMode: setSystemParams accepts mode 2
 
 int device_default() {
   if (g_device >= 0) return g_device;
@@ -175,12 +177,14 @@ pir_engine_t* engine_for(server* s, ShimState* st, int nq, bool upload = true, b
   // the party count only sizes DPF keys; polynomial-PIR setups may have p < 2 or > 17
   c.num_parties = NUM_PARTIES < 2 ? 2 : (NUM_PARTIES > PIR_MAX_PARTIES ? PIR_MAX_PARTIES : NUM_PARTIES);
   c.party_index = s->partyIndex;
-  c.log_num_records = LOG_NUM_ENCODED_FILES;
+  // Shamir: value rows [0, N) and Hermite rows [N, 2N) (the indexList layout, server.cpp:25-32)
+  c.log_num_records = LOG_NUM_ENCODED_FILES + (IS_HERMITE ? 1 : 0);
   c.record_bytes = (uint32_t)ENCODED_FILE_SIZE_BYTES;
   c.num_rounds = nq;
   c.log_num_partitions = 0;
   c.partition_index = 0;
-  c.is_byzantine = s->isByzantine;
+  // the Shamir entry points decide themselves: their Thread form is honest over any range
+  c.is_byzantine = IS_HERMITE ? 0 : s->isByzantine;
   const bool remake = !st->eng || memcmp(&c, &st->cfg, sizeof c) != 0;
   std::unique_lock<std::shared_mutex> excl(st->life, std::defer_lock);
   if (remake || st->dirty) {  // no slice pass may be using the engine or the shard meanwhile
@@ -615,6 +619,21 @@ void hmac_sha256(const uint8_t* key, size_t klen, const uint8_t* msg, size_t mle
 
 }  // namespace
 
+namespace pir_shim {
+
+HermiteEncodeFn g_encode_hermite = nullptr;
+
+void with_engine(server* s, int nq, const std::function<void(pir_engine_t*)>& fn) {
+  ShimState* st = state_of(s);
+  std::lock_guard<std::mutex> lk(st->mu);
+  fn(engine_for(s, st, nq));
+}
+
+void engine_failure(const char* what) { die(what); }
+
+}  // namespace pir_shim
+
+
 extern "C" {
 
 // interpolation.cpp:176-196: coefficients of the degree-funcDegree polynomial through the first
@@ -729,6 +748,8 @@ void assembleHollantiResponses(client* c, uint8_t* erasureIndexList, uint8_t*** 
 
 void pirSetDevice(int device) { g_device = device; }
 
+void pirEnableShamirMode(int on) { g_shamir_mode = on != 0; }
+
 void pirServerShardChanged(server* s) {
   if (!s || !s->ctx) return;
   ShimState* st = static_cast<ShimState*>(s->ctx);
@@ -803,16 +824,21 @@ static bool select_covering(int t, int p, int m) {
 // Goldberg) abort
 void setSystemParams(int logNumFiles, int fileSizeBytes, int t, int k, int r, int b, int rho,
                      int checkMac, int mode) {
-  if (mode != 0 && mode != 1 && mode != 3 && mode != 4) {
+  if (mode == 2 && !g_shamir_mode) {
+    fprintf(stderr, "pir shim: mode 2 is outside the engine's scope in this process (the Shamir "
+            "mode is served after pirEnableShamirMode(1))\n");
+    abort();
+  }
+  if (mode < 0 || mode > 4) {
     fprintf(stderr, "pir shim: mode %d is outside the engine's scope (tree = 0, multiparty = 1, "
-            "Hollanti = 3, covering design = 4)\n", mode);
+            "Shamir = 2 once enabled, Hollanti = 3, covering design = 4)\n", mode);
     abort();
   }
   if (mode == 0 && t != 1) {  // params.cpp:415 assert(T == 1)
     fprintf(stderr, "pir shim: tree mode requires t == 1 (got %d)\n", t);
     abort();
   }
-  if (mode == 3 && checkMac) {
+  if ((mode == 2 || mode == 3) && checkMac) {
     fprintf(stderr, "pir shim: CheckMAC setups are outside the engine's scope\n");
     abort();
   }
@@ -840,7 +866,11 @@ void setSystemParams(int logNumFiles, int fileSizeBytes, int t, int k, int r, in
   } else {
     NUM_PARTIES = K + R + T + 2 * B + (mode == 1 ? 0 : RHO - 1);
   }
-  ENCODE_ACROSS = mode == 3 ? 0 : 1;
+  ENCODE_ACROSS = (mode == 2 || mode == 3) ? 0 : 1;
+  // params.cpp:423-429: ceil((2T + 2K) / 2 + R + 2B + RHO - 1) is the party count above; the
+  // reference never clears IS_HERMITE again, here every setup starts from 0 (like M and isRss)
+  IS_HERMITE = mode == 2 ? 1 : 0;
+  if (mode == 2) D = 2;
   NUM_RESPONSES = NUM_PARTIES - R;
   if (ENCODE_ACROSS) {
     LOG_NUM_ENCODED_FILES = ceil_log2((NUM_FILES + k - 1) / k);
@@ -888,7 +918,8 @@ void initializeServer(server* s, int partyIndex, uint32_t logNumFiles, uint32_t 
   s->ctx = st;
   s->ctxThreads = nullptr;
   s->partyIndex = partyIndex;
-  const uint32_t n = 1u << logNumFiles;
+  // server.cpp:25-32: a Hermite setup holds the derivative rows behind the value rows
+  const uint32_t n = (IS_HERMITE ? 2u : 1u) << logNumFiles;
   // one zeroed allocation for all N rows (the reference mallocs each, server.cpp:34-38): the
   // pages are only touched when rows are written, not by a GPU setup
   s->indexList = (uint8_t**)malloc((size_t)n * sizeof(uint8_t*));
@@ -1263,9 +1294,6 @@ void assembleWoodruffQueryThreadResults(server* s, uint8_t*** in, int numThreads
            (size_t)ENCODED_FILE_SIZE_BYTES);
 }
 
-void runOptShamirDPFQueryThread(server*, uint8_t**, int, int, int, uint8_t**) {
-  out_of_scope("runOptShamirDPFQueryThread", "Shamir");
-}
 // server.cpp:443-492 (both branches compute the honest answer): NUM_CD_KEYS shares of the
 // covering-design key evaluated on the thread's rows and scanned on the engine
 void runCDQueryThread(server* s, uint8_t* key, int threadNum, int numThreads, uint8_t** result) {
@@ -1404,10 +1432,17 @@ void encode_across_files_server(client* c, server* s) {
 // part j = bytes [j*EFS, (j+1)*EFS) of the file zero-padded to K*EFS (encodeMat[j][q-1] of
 // gen_encode_matrix, coding.cpp:64-70).  One 256-entry product table per coefficient.
 void encode_within_files_server(client* c, server* s) {
-  if (IS_HERMITE) out_of_scope("encode_within_files_server (Hermite rows)", "Shamir");
+  if (IS_HERMITE && !pir_shim::g_encode_hermite)
+    out_of_scope("encode_within_files_server (Hermite rows)", "Shamir");
   if (gpu_setup(s, [&](pir_engine_t* e) {
-        return pir_engine_encode_within_rows(e, c->unencoded_files, (uint64_t)NUM_FILES,
-                                             FILE_SIZE_BYTES, K, s->partyIndex);
+        // value rows (the rows past NUM_FILES, a Shamir engine's Hermite half, are zeroed),
+        // then the Hermite rows [N, 2N)
+        int rc = pir_engine_encode_within_rows(e, c->unencoded_files, (uint64_t)NUM_FILES,
+                                               FILE_SIZE_BYTES, K, s->partyIndex);
+        if (rc == PIR_OK && IS_HERMITE)
+          rc = pir_shim::g_encode_hermite(e, c->unencoded_files, (uint64_t)NUM_FILES,
+                                          FILE_SIZE_BYTES, K, s->partyIndex);
+        return rc;
       }))
     return;
   const int efs = ENCODED_FILE_SIZE_BYTES;
@@ -1421,6 +1456,18 @@ void encode_within_files_server(client* c, server* s) {
     const uint8_t* f = c->unencoded_files[i];
     for (int j = 0; j < K; ++j) {
       const uint8_t* t = &tab[(size_t)j * 256];
+      for (int b = 0; b < efs; ++b) {
+        const long src = (long)j * efs + b;
+        if (src < (long)FILE_SIZE_BYTES) row[b] ^= t[f[src]];
+      }
+    }
+  }
+  // client.cpp:57-68, 103-107: Hermite row i = XOR over odd j of gf_pow(q, j - 1) * part j
+  for (int i = 0; IS_HERMITE && i < NUM_ENCODED_FILES; ++i) {
+    uint8_t* row = s->indexList[NUM_ENCODED_FILES + i];
+    const uint8_t* f = c->unencoded_files[i];
+    for (int j = 1; j < K; j += 2) {
+      const uint8_t* t = &tab[(size_t)(j - 1) * 256];
       for (int b = 0; b < efs; ++b) {
         const long src = (long)j * efs + b;
         if (src < (long)FILE_SIZE_BYTES) row[b] ^= t[f[src]];

@@ -1,0 +1,29 @@
+// pir_server_internal.h -- the seam between pir_server.cpp and the translation units that add
+// modes to the shim (pir_server_shamir.cpp).  Not part of the C ABI.
+//
+// pir_server.cpp names no engine entry point newer than its own modes need, so that it links
+// against a stub of the engine (tests/tsan); a mode's unit reaches the server's engine through
+// with_engine and hands pir_server.cpp what its setup needs through the hooks below.
+#pragma once
+#include <stdint.h>
+
+#include <functional>
+
+#include "../../include/pir_engine.h"
+#include "../../include/pir_server.h"
+
+namespace pir_shim {
+
+// fn(engine) under the server's lock, the engine made for nq rounds and holding the server's
+// current rows (what every query entry point of pir_server.cpp does first)
+void with_engine(server* s, int nq, const std::function<void(pir_engine_t*)>& fn);
+// "pir engine failure in <what>: <last error>" and abort (the reference's handleErrors())
+[[noreturn]] void engine_failure(const char* what);
+
+// The Hermite half of encode_within_files_server's GPU setup: pir_engine_encode_hermite_rows,
+// registered by pir_server_shamir.cpp when it is linked (nullptr otherwise: the setup refuses).
+using HermiteEncodeFn = int (*)(pir_engine_t*, const uint8_t* const* files, uint64_t num_files,
+                                uint32_t file_bytes, int k, int party);
+extern HermiteEncodeFn g_encode_hermite;
+
+}  // namespace pir_shim

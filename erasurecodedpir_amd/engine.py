@@ -115,6 +115,25 @@ class Engine:
             if d_f is not None:
                 self.free_dev(d_f)
 
+    def encode_hermite(self, num_files, file_bytes, k, files=None, party=0):
+        """The Hermite rows [N, 2N) of a Shamir engine (log_num_records = n + 1) computed on the
+        GPU (client.cpp:57-68, 103-107): the formal derivative of the within-file polynomial
+        that encode_within evaluates.  files / party as for encode_within; the value rows
+        [0, N) are left alone (call encode_within first: it zeroes the rows past num_files)."""
+        d_f, pitch = None, 0
+        if files is not None:
+            f = np.ascontiguousarray(np.asarray(files, np.uint8).reshape(num_files, -1))
+            pitch = f.shape[1]
+            d_f = self.alloc_dev(max(1, f.size))
+        try:
+            if d_f is not None:
+                self.h2d(d_f, f.reshape(-1))
+            check(self._lib.pir_engine_encode_hermite_dev(self._h, d_f, pitch, num_files,
+                                                          file_bytes, k, party), "encode_hermite")
+        finally:
+            if d_f is not None:
+                self.free_dev(d_f)
+
     def shard_row(self, i):
         out = np.empty(self.record_bytes, np.uint8)
         check(self._lib.pir_engine_get_shard_row(self._h, i, out.ctypes.data_as(ctypes.c_void_p)),
@@ -215,6 +234,38 @@ class Engine:
     def answer_coefs_dev(self, d_coefs, coef_pitch, row0, nrows, d_result, stream=None):
         check(self._lib.pir_engine_answer_coefs_dev(self._h, d_coefs, coef_pitch, row0, nrows,
                                                     d_result, stream), "answer_coefs_dev")
+
+    @property
+    def shamir_key_len(self):
+        """calcShamirDPFKeyLength of a Shamir engine (log_num_records = n + 1): 2^x + 2^y."""
+        n = self.n - 1
+        x = (n + 1) // 2
+        return (1 << x) + (1 << (n - x))
+
+    @property
+    def shamir_response_len(self):
+        return shamir_response_len(self.n - 1, self.record_bytes)
+
+    def answer_shamir(self, keys, rec0=0, nrec=None):
+        """Shamir sqrt(N) answer (runOptShamirDPFQuery[Thread], src/c/server.cpp:203-319) of a
+        Shamir engine (value rows [0, N), Hermite rows [N, 2N)): keys is (num_rounds, 2^x + 2^y)
+        uint8; the records [rec0, rec0 + nrec) of the N-record domain are answered.
+        -> (num_rounds, 2^x + 2^y + 2, record_bytes): row sums, column sums, the Hermite total
+        and the value total."""
+        kl = self.shamir_key_len
+        k = np.ascontiguousarray(np.asarray(keys, np.uint8).reshape(self.num_rounds, kl))
+        nrec = self.num_rows // 2 - rec0 if nrec is None else nrec
+        ptrs = (ctypes.c_void_p * self.num_rounds)(*[k[a].ctypes.data
+                                                     for a in range(self.num_rounds)])
+        out = np.empty((self.num_rounds, kl + 2, self.record_bytes), np.uint8)
+        check(self._lib.pir_engine_answer_shamir(self._h, ptrs, rec0, nrec,
+                                                 out.ctypes.data_as(ctypes.c_void_p)),
+              "pir_engine_answer_shamir")
+        return out
+
+    def answer_shamir_dev(self, d_keys, key_pitch, rec0, nrec, d_result, stream=None):
+        check(self._lib.pir_engine_answer_shamir_dev(self._h, d_keys, key_pitch, rec0, nrec,
+                                                     d_result, stream), "answer_shamir_dev")
 
     def answer_mp(self, key, p, t, thread_num=0, num_threads=1):
         """Multiparty sqrt(N) DPF answer (runOptimizedMultiPartyDPFQuery[Thread], src/c/
@@ -385,6 +436,11 @@ class Engine:
                 "rccl_user_rank": ci.user_rank, "rccl_device": ci.device,
                 "engine_device": ci.engine_device,
                 "pci_bus_id": ci.pci_bus_id.decode(errors="replace")}
+
+
+def shamir_response_len(log_domain, record_bytes):
+    """calcShamirResponseLength: (2^x + 2^y + 2) * record_bytes, x = ceil(n/2), y = n - x."""
+    return int(_lib.load().pir_engine_shamir_response_len(log_domain, record_bytes))
 
 
 def mp_num_keys(p, t):

@@ -15,6 +15,21 @@ def setSystemParams(logNumFiles, fileSizeBytes, t, k, r, b, rho, checkMac, mode)
     _lib.load().setSystemParams(logNumFiles, fileSizeBytes, t, k, r, b, rho, checkMac, mode)
 
 
+def enable_shamir_mode(on=True):
+    """pirEnableShamirMode: setSystemParams accepts mode 2 (Shamir sqrt(N)) in this process; a
+    plain process refuses it."""
+    _lib.load().pirEnableShamirMode(int(bool(on)))
+
+
+def calcShamirDPFKeyLength(log_domain_size):
+    """utils.cpp:131-143: 2^x + 2^y bytes per round."""
+    return _lib.load().calcShamirDPFKeyLength(log_domain_size)
+
+
+def calcShamirResponseLength(log_domain_size, file_size_bytes):
+    return _lib.load().calcShamirResponseLength(log_domain_size, file_size_bytes)
+
+
 def params():
     """The sizing globals of src/c/params.h:9-33 as a dict."""
     return {n: _lib.global_int(n) for n in _lib.GLOBALS_INT + _lib.GLOBALS_U32}
@@ -41,7 +56,8 @@ class Server:
         self.s = CServer()
         self._lib.initializeServer(ctypes.byref(self.s), partyIndex, logNumFiles, fileSizeBytes,
                                    isByzantine, numThreads)
-        self.rows = 1 << logNumFiles
+        # a Hermite (Shamir, mode 2) setup holds 2N rows: values, then derivative rows
+        self.rows = (2 if _lib.global_int("IS_HERMITE") else 1) << logNumFiles
         self.file_size = fileSizeBytes
 
     @property
@@ -112,6 +128,33 @@ class Server:
             self._lib.runHollantiQuery(ctypes.byref(self.s), kp, _row_ptrs(out))
         else:
             self._lib.runHollantiQueryThread(ctypes.byref(self.s), kp, *thread, _row_ptrs(out))
+        return out
+
+    def runOptShamirDPFQuery(self, keys):
+        """Shamir sqrt(N) answer over every record (server.cpp:203-239): keys (NUM_ROUNDS,
+        calcShamirDPFKeyLength) -> (NUM_ROUNDS, calcShamirResponseLength)."""
+        return self._shamir(keys, None)
+
+    def runOptShamirDPFQueryThread(self, keys, threadNum, startIndex, endIndex):
+        """Records [startIndex, endIndex) (server.cpp:241-302)."""
+        return self._shamir(keys, (threadNum, startIndex, endIndex))
+
+    def _shamir(self, keys, thread):
+        efs = _lib.global_int("ENCODED_FILE_SIZE_BYTES")
+        nq = _lib.global_int("NUM_ROUNDS")
+        n = _lib.global_int("LOG_NUM_ENCODED_FILES")
+        kl = calcShamirDPFKeyLength(n)
+        k = np.ascontiguousarray(np.asarray(keys, np.uint8))
+        if k.size != nq * kl:  # the shim reads NUM_ROUNDS keys of calcShamirDPFKeyLength bytes
+            raise ValueError(f"Shamir keys of {k.size} bytes, expected {nq} x {kl}")
+        k = k.reshape(nq, kl)
+        out = np.zeros((nq, calcShamirResponseLength(n, efs)), np.uint8)
+        kp = _row_ptrs(k)
+        if thread is None:
+            self._lib.runOptShamirDPFQuery(ctypes.byref(self.s), kp, _row_ptrs(out))
+        else:
+            self._lib.runOptShamirDPFQueryThread(ctypes.byref(self.s), kp, *thread,
+                                                 _row_ptrs(out))
         return out
 
     def runOptimizedMultiPartyDPFQuery(self, key):
@@ -191,6 +234,12 @@ def assemblDPFTreeQueryThreadResults(server, parts):
 def assembleHollantiQueryThreadResults(server, parts):
     """parts: (numThreads, NUM_ROUNDS, EFS) -> (NUM_ROUNDS, EFS) (src/c/server.cpp:373-382)."""
     return _assemble("assembleHollantiQueryThreadResults", server, parts)
+
+
+def assembleShamirQueryThreadResults(server, parts):
+    """parts: (numThreads, NUM_ROUNDS, response_len) -> (NUM_ROUNDS, response_len)
+    (server.cpp:304-319)."""
+    return _assemble("assembleShamirQueryThreadResults", server, parts)
 
 
 def assembleMultipartyDPFQueryThreadResults(server, parts):

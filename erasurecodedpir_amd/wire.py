@@ -17,6 +17,7 @@ import numpy as np
 # common.go:147-154
 SETUP_REQUEST, TREE_SEARCH_REQUEST, MULTIPARTY_SEARCH_REQUEST, HOLLANTI_SEARCH_REQUEST = 0, 1, 3, 4
 CD732_SEARCH_REQUEST, TEST_REQUEST = 5, 7
+SHAMIR_SEARCH_REQUEST = 2
 
 
 class WireError(RuntimeError):
@@ -71,7 +72,7 @@ class Conn:
 def setup(addr, log_num_files, file_size_bytes, k, r, rho=1, num_threads=1, is_byzantine=0,
           mode=0, t=1, b=0):
     """SETUP_REQUEST with the fields of common.go:51-65 (no MAC): mode 0 tree, 1 multiparty,
-    3 Hollanti, 4 covering design."""
+    2 Shamir, 3 Hollanti, 4 covering design."""
     host, port = addr
     req = {"BenchmarkDir": "", "LogNumFiles": log_num_files, "FileSizeBytes": file_size_bytes,
            "T": t, "K": k, "R": r, "B": b, "Rho": rho, "Mode": mode, "IsByzantine": is_byzantine,
@@ -105,6 +106,15 @@ def hollanti_search(addr, keys):
     host, port = addr
     with Conn(host, port) as c:
         return c.call(HOLLANTI_SEARCH_REQUEST, {"Key": [bytes(np.asarray(k, np.uint8)) for k in keys]})
+
+
+def shamir_query(addr, keys):
+    """SHAMIR_SEARCH_REQUEST (server_util/shamir.go:16-130): keys = NUM_ROUNDS keys of
+    calcShamirDPFKeyLength(LOG_NUM_ENCODED_FILES) bytes (ky then kx); Results = NUM_ROUNDS
+    responses of calcShamirResponseLength bytes (row sums, column sums, the two totals)."""
+    host, port = addr
+    with Conn(host, port) as c:
+        return c.call(SHAMIR_SEARCH_REQUEST, {"Key": [bytes(np.asarray(k, np.uint8)) for k in keys]})
 
 
 def tree_query(addrs, index, log_num_files, file_size_bytes, k, r, rho=1, device=0):

@@ -17,6 +17,9 @@
  *                                    (src/server_util/tree.go:60-76)        server.cpp:505-549
  *   pir_engine_eval_all              evalAllOptimizedDPF                    dpf_tree.cpp:473-598
  *   pir_engine_answer_coefs[_dev]    runHollantiQuery / ...Thread           server.cpp:321-371
+ *   pir_engine_answer_shamir[_dev]   runOptShamirDPFQuery / ...Thread       server.cpp:203-302
+ *   pir_engine_encode_hermite_*      generate_hermite_within_file           client.cpp:57-68
+ *   pir_engine_shamir_response_len   calcShamirResponseLength               utils.cpp:140-143
  *   pir_engine_answer_mp[_dev]       runOptimizedMultiPartyDPFQuery[Thread] server.cpp:136-176,
  *                                    (evalAllOptMultiPartyDPF[Thread])      :384-430,
  *                                                                 multiparty_dpf.cpp:467-615
@@ -148,6 +151,38 @@ int pir_engine_answer_coefs(pir_engine_t *e, const uint8_t *const *coefs, uint64
 /* device form: round a's coefficient of engine row r at d_coefs[a * coef_pitch + r] */
 int pir_engine_answer_coefs_dev(pir_engine_t *e, const uint8_t *d_coefs, uint64_t coef_pitch,
                                 uint64_t row0, uint64_t nrows, uint8_t *d_result, void *stream);
+/* ---- Shamir sqrt(N) mode (runOptShamirDPFQuery / ...Thread, server.cpp:203-319) ----
+ * A Shamir engine is created with log_num_records = n + 1 and no partitions: rows [0, N), N =
+ * 2^n, are the value rows and rows [N, 2N) the derivative ("Hermite") rows, the reference's
+ * indexList layout (set_shard / get_shard address all 2N).  The value rows are a 2^x x 2^y
+ * matrix, x = ceil(n/2), y = n - x, record i at delta = i >> y, gamma = i & (2^y - 1).  Round
+ * a's key is 2^x + 2^y bytes: ky[delta] = key[a][delta], kx[gamma] = key[a][2^x + gamma].  Its
+ * response is response_len = (2^x + 2^y + 2) * record_bytes bytes, over GF(2^8)/0x11d:
+ *   record delta          Rx[delta] = XOR_gamma kx[gamma] * A[delta][gamma]
+ *   record 2^x + gamma    Ry[gamma] = XOR_delta ky[delta] * A[delta][gamma]
+ *   record 2^x + 2^y      XOR kx[gamma] ky[delta] * H[delta][gamma]
+ *   record 2^x + 2^y + 1  XOR kx[gamma] ky[delta] * A[delta][gamma]
+ * with every sum restricted to the records [rec0, rec0 + nrec) of the domain (the Thread form's
+ * [startIndex, endIndex); partial responses XOR to the whole).  result: num_rounds x
+ * response_len bytes.  A Byzantine engine answers the whole-domain call (rec0 = 0, nrec = N)
+ * with random bytes and every other range honestly, as the reference's two entry points do.
+ * Three shard-sized passes (value rows twice, Hermite rows once) per group of up to 4 rounds. */
+uint64_t pir_engine_shamir_response_len(int log_domain, uint32_t record_bytes);
+int pir_engine_answer_shamir(pir_engine_t *e, const uint8_t *const *keys, uint64_t rec0,
+                             uint64_t nrec, uint8_t *result);
+/* device form: round a's key at d_keys + a * key_pitch; asynchronous on `stream` */
+int pir_engine_answer_shamir_dev(pir_engine_t *e, const uint8_t *d_keys, uint64_t key_pitch,
+                                 uint64_t rec0, uint64_t nrec, uint8_t *d_result, void *stream);
+/* the Hermite rows [N, 2N) of a Shamir engine (client.cpp:57-68, 103-107): row N + r = XOR over
+ * odd j, 1 <= j < k, of gf_pow(party, j - 1) * part j of file r -- the formal derivative of the
+ * within-file polynomial that pir_engine_encode_within_* evaluates; rows past num_files are
+ * zero.  Files, synthetic database (d_files = NULL) and party as for encode_within.  The value
+ * rows are not touched.  pir_engine_encode_within_* knows nothing of the two halves and zeroes
+ * the rows past num_files: on a Shamir engine call it first, then this. */
+int pir_engine_encode_hermite_dev(pir_engine_t *e, const uint8_t *d_files, uint64_t file_pitch,
+                                  uint64_t num_files, uint32_t file_bytes, int k, int party);
+int pir_engine_encode_hermite_rows(pir_engine_t *e, const uint8_t *const *files,
+                                   uint64_t num_files, uint32_t file_bytes, int k, int party);
 /* Multiparty sqrt(N) DPF answer of party index 1..p with threshold t (the engine must have
  * num_rounds == pir_engine_mp_num_keys(p, t), one output share per round):
  *   result[a] = XOR_{r in rows} share[a][r] * shard row r,   a < NUM_RSS_KEYS,
@@ -237,7 +272,9 @@ int pir_engine_memcpy_d2h(pir_engine_t *e, void *h_dst, const void *d_src, size_
  * scan.  `slots` event sets are kept in a ring (0 = off), each remembering its answer's path;
  * last_timings averages the answers recorded since the previous read (at most `slots`), every
  * slot read by its own path and reported under the newest answer's phase names, fills up to
- * `max` {name, ms} pairs and returns the count. */
+ * `max` {name, ms} pairs and returns the count.  A Shamir answer (fused = 4) reports k_query's
+ * phase names: launch = start -> the response zeroed, scan = the rows pass, the strips pass and
+ * the Hermite scan, reduce = the Hermite slabs' k_reduce + the totals kernel. */
 typedef struct {
     char name[32];
     float ms;

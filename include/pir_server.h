@@ -174,12 +174,25 @@ void assembleMultipartyDPFQueryThreadResults(server *s, uint8_t ***in, int numTh
 void runCDQueryThread(server *s, uint8_t *key, int threadNum, int numThreads, uint8_t **result);
 void assembleCDQueryThreadResults(server *s, uint8_t ***in, int numThreads, uint8_t **out);
 
-/* ---- the other PIR modes' server entry points, bound by src/server_util/ (shamir.go:52,
- *      woodruff.go:69).  Their modes are outside this engine's scope: setSystemParams refuses
- *      modes 2, 5, 6, and these abort with a message if reached anyway.  The assemble functions
- *      are the reference's XOR folds (server.cpp:304-319, 647-665). ---- */
+/* ---- Shamir sqrt(N) PIR (mode 2, src/server_util/shamir.go:52): the row/column GF(2^8) scan of
+ *      runOptShamirDPFQuery[Thread] (server.cpp:203-302) on the engine
+ *      (pir_engine_answer_shamir).  Opt-in per process: setSystemParams refuses mode 2 until
+ *      pirEnableShamirMode(1) has been called; with it, mode 2 sizes as params.cpp:423-429,
+ *      495-512 (IS_HERMITE = 1, D = 2, files encoded within), initializeServer allocates 2N rows
+ *      (values, then Hermite rows) and encode_within_files_server encodes both halves.
+ *      keys[a], a < NUM_ROUNDS, = calcShamirDPFKeyLength(LOG_NUM_ENCODED_FILES) bytes; result[a]
+ *      = calcShamirResponseLength(LOG_NUM_ENCODED_FILES, ENCODED_FILE_SIZE_BYTES) bytes.  The
+ *      whole-domain form answers random bytes for a Byzantine server; the Thread form answers
+ *      records [startIndex, endIndex) honestly either way (as the reference's does).  CheckMAC
+ *      setups are refused. ---- */
+void pirEnableShamirMode(int on);
+void runOptShamirDPFQuery(server *s, uint8_t **keys, uint8_t **result);
 void runOptShamirDPFQueryThread(server *s, uint8_t **keys, int threadNum, int startIndex,
                                 int endIndex, uint8_t **result);
+/* ---- the Woodruff mode's server entry point, bound by src/server_util/woodruff.go:69.  The
+ *      mode is outside this engine's scope: setSystemParams refuses modes 5, 6, and this aborts
+ *      with a message if reached anyway.  The assemble functions are the reference's XOR folds
+ *      (server.cpp:304-319, 647-665). ---- */
 void runWoodruffQueryThread(server *s, uint8_t *key, int threadNum, int startIndex, int endIndex,
                             uint8_t **result);
 void assembleShamirQueryThreadResults(server *s, uint8_t ***in, int numThreads, uint8_t **out);
