@@ -104,6 +104,13 @@ PROTOTYPES = {
     "pir_engine_answer_shamir_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
     "pir_engine_encode_hermite_dev": (_I, [_P, _P, _U64, _U64, _U32, _I, _I]),
     "pir_engine_encode_hermite_rows": (_I, [_P, _P, _U64, _U32, _I, _I]),
+    "pir_engine_woodruff_m": (_U32, [_I]),
+    "pir_engine_woodruff_pair": (_I, [_U32, _U64, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "pir_engine_woodruff_fused_tile": (_I, [_P]),
+    "pir_engine_answer_woodruff": (_I, [_P, _P, _U64, _U64, _U64, _P]),
+    "pir_engine_answer_woodruff_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
+    "pir_engine_answer_woodruff_deriv": (_I, [_P, _P, _U64, _U64, _U64, _P]),
+    "pir_engine_answer_woodruff_deriv_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
     "pir_engine_answer_mp": (_I, [_P, _P, _U64, _I, _I, _I, _I, _P]),
     "pir_engine_answer_mp_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "pir_engine_mp_num_keys": (_I, [_I, _I]),

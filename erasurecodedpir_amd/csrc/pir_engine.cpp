@@ -27,6 +27,7 @@
 #include "pir_kernels.h"
 #include "pir_mp.h"
 #include "pir_shamir.h"
+#include "pir_woodruff.h"
 
 #ifndef PIR_TRACE_TREE_TILES
 #define PIR_TRACE_TREE_TILES 0  // diagnostics build only (pir_kernels.hip)
@@ -163,7 +164,8 @@ struct pir_engine {
   int fused_reduce = 0;
   uint8_t* d_coef_stage = nullptr;  // explicit-coefficient answers: host vectors staged here
   size_t coef_stage_cap = 0;
-  uint8_t* d_shamir_res = nullptr;  // Shamir answers through the host API: nq x response_len
+  // Shamir answers through the host API: nq x response_len; Woodruff derivative answers too
+  uint8_t* d_shamir_res = nullptr;
   size_t shamir_res_cap = 0;
   uint8_t* d_mpkey = nullptr;       // multiparty DPF keys: host keys / unaligned device keys
   size_t mpkey_cap = 0;
@@ -704,6 +706,10 @@ constexpr int kNumPhases = 9;
 // A Shamir answer (fused == 4) uses the same five events: "launch" = answer start -> the response
 // zeroed, "scan" = the rows pass, the strips pass and the Hermite scan, "reduce" = k_reduce of
 // the Hermite slabs + k_shamir_totals
+// A Woodruff answer (fused == 5: k_query's Woodruff mode, 6: k_woodruff_coefs + the scan) too:
+// "launch" = answer start -> its first kernel, "scan" = that kernel (with 6, both), "reduce" =
+// k_reduce; its derivative answers (fused == 7): "launch" = start -> the answer zeroed, "scan" =
+// the rows pass, the totals kernel and the columns pass, "reduce" = 0
 const char* const kQueryPhaseNames[] = {"launch", "scan", "reduce", "comm_fold", "total", "fused"};
 constexpr int kNumQueryPhases = 6;
 
@@ -1028,6 +1034,116 @@ int check_shamir(const pir_engine* e, uint64_t rec0, uint64_t nrec) {
   if (rec0 > N || nrec > N - rec0)
     return fail(PIR_EINVAL, "records [%llu,%llu) beyond the %llu value rows",
                 (unsigned long long)rec0, (unsigned long long)(rec0 + nrec), (unsigned long long)N);
+  return PIR_OK;
+}
+
+// Woodruff value answer (server.cpp:564-616) over the records [rec0, rec0 + nrec): out = XOR_i
+// key[a_i] * key[b_i] * row_i, (a_i, b_i) the i-th 2-subset of [0, M) (pir_woodruff.h).
+// The whole domain of a shape k_query tiles: ONE launch, its builder waves writing each tile's
+// pair products into the LDS ring while the scan waves stream the shard (fused = 5).  Every
+// other range or shape: k_woodruff_coefs, then the explicit-coefficient scan (fused = 6).
+// $PIR_WD_FUSED: 0 = never k_query, 2 = always (an answer it cannot take fails: tests), default
+// = the policy: k_query wherever it takes the answer.  Measured with tools/bench_woodruff.py on
+// one MI355X, the three legs alternated in one process (profiles/woodruff/): 2^24 x 1 KiB
+// k_query 2.456 ms against 2.554 (coefficient kernel + scan) and 2.539 (answer_coefs), the
+// spread between repeats of one leg 0.05 ms; 2^24 x 256 B 0.634 against 0.746 / 0.715; 2^20 x
+// 1 KiB 0.178 against 0.188 / 0.181 and 2^22 x 2 KiB 1.258 against 1.255 / 1.251, both inside
+// the spread (0.01 / 0.04 ms).
+// Both paths use the five-event profiling layout: "launch" = answer start -> the first kernel,
+// "scan" = k_woodruff_coefs + the scan, or k_query, "reduce" = k_reduce.
+constexpr bool kWdFusedDefault = true;
+
+bool woodruff_fused_takes(const pir_engine* e, pir::QueryPlan* qp) {
+  const auto& c = e->cfg;
+  *qp = pir::make_query_plan(c.log_num_records, 0, 2, 1, e->pitch, e->num_cus);
+  return e->allow_query && pir::query_wd_takes(*qp);
+}
+
+int answer_woodruff_locked(pir_engine* e, const uint8_t* d_key, uint32_t M, uint64_t rec0,
+                           uint64_t nrec, uint8_t* d_result, hipStream_t s) {
+  const auto& c = e->cfg;
+  e->ev = nullptr;
+  const char* fv = getenv("PIR_WD_FUSED");
+  const int fmode = fv ? atoi(fv) : 1;
+  pir::QueryPlan qp{};
+  const bool whole = rec0 == 0 && nrec == e->rows;
+  const bool takes = fmode != 0 && whole && woodruff_fused_takes(e, &qp);
+  if (!takes && fmode == 2)
+    return fail(PIR_EINVAL, "k_query's Woodruff mode does not take this answer ($PIR_WD_FUSED=2)");
+  const bool fused = takes && (fmode == 2 || kWdFusedDefault);
+  hipEvent_t* ev = nullptr;
+  if (!e->prof.empty()) {
+    ev = prof_slot(e, fused ? 5 : 6, 1, true);
+    HIP_TRY(hipEventRecord(ev[EV_START], s));
+  }
+  if (fused) {
+    if (int rc = ensure_slabs(e, pir::query_slab_bytes(qp))) return rc;
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
+    HIP_TRY(pir::launch_query_wd(qp, d_key, M, c.log_num_records, e->d_shard, e->d_slabs, s));
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_E], s));
+    HIP_TRY(pir::launch_reduce(qp.shape, e->d_slabs, c.record_bytes, d_result, s));
+    e->last_fused = 5;
+  } else if (nrec == 0) {
+    if (ev)
+      for (int i : {EV_SCAN_B, EV_SCAN_E}) HIP_TRY(hipEventRecord(ev[i], s));
+    HIP_TRY(hipMemsetAsync(d_result, 0, c.record_bytes, s));
+  } else {
+    const pir::ScanShape sh = pir::make_scan_shape(nrec, e->pitch, 1, e->num_cus);
+    if (int rc = ensure_slabs(e, (size_t)sh.grid.x * sh.grid.y * sh.slab_bytes)) return rc;
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
+    HIP_TRY(pir::launch_woodruff_coefs(d_key, M, e->nrp, rec0, rec0 + nrec, e->d_c, s));
+    HIP_TRY(pir::launch_scan(sh, e->d_shard + rec0 * e->pitch, nrec, e->d_c, e->d_slabs, false, s));
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_E], s));
+    HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, d_result, s));
+    e->last_fused = 6;
+  }
+  if (ev) {
+    HIP_TRY(hipEventRecord(ev[EV_RED], s));
+    HIP_TRY(hipEventRecord(ev[EV_END], s));
+  }
+  return PIR_OK;
+}
+
+// Woodruff derivative answers (server.cpp:618-644): M + 1 records at d_result, all overwritten
+// (the reference zeroes only the first and XORs into whatever the caller's other M held).  Two
+// passes over the shard (pir_woodruff.h).  Five-event layout, fused = 7: "launch" = answer start
+// -> the answer zeroed, "scan" = the rows pass, the totals kernel and the columns pass, "reduce"
+// = 0.
+int answer_woodruff_deriv_locked(pir_engine* e, const uint8_t* d_key, uint32_t M, uint64_t rec0,
+                                 uint64_t nrec, uint8_t* d_result, hipStream_t s) {
+  const auto& c = e->cfg;
+  e->ev = nullptr;
+  hipEvent_t* ev = nullptr;
+  if (!e->prof.empty()) {
+    ev = prof_slot(e, 7, 1, true);
+    HIP_TRY(hipEventRecord(ev[EV_START], s));
+  }
+  HIP_TRY(hipMemsetAsync(d_result, 0, (size_t)(M + 1) * c.record_bytes, s));
+  if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
+  HIP_TRY(pir::launch_woodruff_deriv(e->d_shard, e->pitch, c.record_bytes, d_key, M, rec0,
+                                     rec0 + nrec, d_result, s));
+  e->last_fused = 7;
+  if (ev)
+    for (int i : {EV_SCAN_E, EV_RED, EV_END}) HIP_TRY(hipEventRecord(ev[i], s));
+  return PIR_OK;
+}
+
+// a Woodruff engine holds the N = 2^n records unsplit and answers one round
+int check_woodruff(const pir_engine* e, uint64_t key_len, uint64_t rec0, uint64_t nrec) {
+  const auto& c = e->cfg;
+  if (c.num_rounds != 1)
+    return fail(PIR_EINVAL, "the Woodruff mode answers one round (the engine has %d)", c.num_rounds);
+  if (c.log_num_partitions > 0)
+    return fail(PIR_EINVAL, "the Woodruff mode does not serve a split shard (2^%d partitions)",
+                c.log_num_partitions);
+  if (e->comm) return fail(PIR_EINVAL, "the Woodruff mode does not answer through a communicator");
+  const uint32_t M = pir::wd_key_len(c.log_num_records);
+  if (!M || key_len != M)
+    return fail(PIR_EINVAL, "Woodruff key of %llu bytes; 2^%d records take M = %u",
+                (unsigned long long)key_len, c.log_num_records, M);
+  if (rec0 > e->rows || nrec > e->rows - rec0)
+    return fail(PIR_EINVAL, "records [%llu,%llu) beyond the %llu records", (unsigned long long)rec0,
+                (unsigned long long)(rec0 + nrec), (unsigned long long)e->rows);
   return PIR_OK;
 }
 
@@ -1995,6 +2111,92 @@ int pir_engine_encode_hermite_rows(pir_engine_t* e, const uint8_t* const* files,
     (void)hipFree(d_files);
   }
   return rc;
+}
+
+uint32_t pir_engine_woodruff_m(int log_num_records) { return pir::wd_key_len(log_num_records); }
+
+int pir_engine_woodruff_pair(uint32_t m, uint64_t i, uint32_t* a, uint32_t* b) {
+  if (!a || !b) return fail(PIR_EINVAL, "null argument");
+  if (m < 3 || m >= (1u << 17) || i >= (uint64_t)m * (m - 1) / 2)
+    return fail(PIR_EINVAL, "no pair of rank %llu among the 2-subsets of [0,%u)",
+                (unsigned long long)i, m);
+  const pir::WdPair p = pir::wd_pair(m, i);
+  *a = p.a;
+  *b = p.b;
+  return PIR_OK;
+}
+
+int pir_engine_woodruff_fused_tile(pir_engine_t* e) {
+  if (!e || e->cfg.num_rounds != 1 || e->cfg.log_num_partitions > 0) return 0;
+  pir::QueryPlan qp{};
+  return woodruff_fused_takes(e, &qp) ? qp.tile : 0;
+}
+
+int pir_engine_answer_woodruff_dev(pir_engine_t* e, const uint8_t* d_key, uint64_t key_len,
+                                   uint64_t rec0, uint64_t nrec, uint8_t* d_result,
+                                   void* stream) {
+  if (!e || !d_result || !d_key) return fail(PIR_EINVAL, "null argument");
+  if (int rc = check_woodruff(e, key_len, rec0, nrec)) return rc;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = ws_acquire(e, s)) return rc;
+  return ws_release(e, s, answer_woodruff_locked(e, d_key, (uint32_t)key_len, rec0, nrec,
+                                                 d_result, s));
+}
+
+int pir_engine_answer_woodruff(pir_engine_t* e, const uint8_t* key, uint64_t key_len,
+                               uint64_t rec0, uint64_t nrec, uint8_t* result) {
+  if (!e || !result || !key) return fail(PIR_EINVAL, "null argument");
+  if (int rc = check_woodruff(e, key_len, rec0, nrec)) return rc;
+  const auto& c = e->cfg;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(c.device));
+  if (int rc = ws_acquire(e, e->stream)) return rc;
+  if (int rc = ensure_buf(&e->d_coef_stage, &e->coef_stage_cap, (size_t)key_len)) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_coef_stage, key, key_len, hipMemcpyHostToDevice, e->stream));
+  int rc = ws_release(e, e->stream, answer_woodruff_locked(e, e->d_coef_stage, (uint32_t)key_len,
+                                                           rec0, nrec, e->d_result, e->stream));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(e->h_res, e->d_result, c.record_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  memcpy(result, e->h_res, c.record_bytes);
+  return PIR_OK;
+}
+
+int pir_engine_answer_woodruff_deriv_dev(pir_engine_t* e, const uint8_t* d_key, uint64_t key_len,
+                                         uint64_t rec0, uint64_t nrec, uint8_t* d_result,
+                                         void* stream) {
+  if (!e || !d_result || !d_key) return fail(PIR_EINVAL, "null argument");
+  if (int rc = check_woodruff(e, key_len, rec0, nrec)) return rc;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = ws_acquire(e, s)) return rc;
+  return ws_release(e, s, answer_woodruff_deriv_locked(e, d_key, (uint32_t)key_len, rec0, nrec,
+                                                       d_result, s));
+}
+
+int pir_engine_answer_woodruff_deriv(pir_engine_t* e, const uint8_t* key, uint64_t key_len,
+                                     uint64_t rec0, uint64_t nrec, uint8_t* result) {
+  if (!e || !result || !key) return fail(PIR_EINVAL, "null argument");
+  if (int rc = check_woodruff(e, key_len, rec0, nrec)) return rc;
+  const auto& c = e->cfg;
+  const size_t out_bytes = (size_t)(key_len + 1) * c.record_bytes;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(c.device));
+  if (int rc = ws_acquire(e, e->stream)) return rc;
+  int rc = ensure_buf(&e->d_coef_stage, &e->coef_stage_cap, (size_t)key_len);
+  if (!rc) rc = ensure_buf(&e->d_shamir_res, &e->shamir_res_cap, out_bytes);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_coef_stage, key, key_len, hipMemcpyHostToDevice, e->stream));
+  rc = ws_release(e, e->stream, answer_woodruff_deriv_locked(e, e->d_coef_stage, (uint32_t)key_len,
+                                                             rec0, nrec, e->d_shamir_res,
+                                                             e->stream));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(result, e->d_shamir_res, out_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return PIR_OK;
 }
 
 int pir_engine_mp_num_keys(int p, int t) {  // params.cpp:618

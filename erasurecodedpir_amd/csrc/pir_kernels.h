@@ -215,6 +215,15 @@ struct MpLayout;
 hipError_t launch_query_mp(const QueryPlan& qp, const uint8_t* d_key, uint32_t key_stride,
                            int nk, const MpLayout& L, int n, int log_parts, uint64_t prefix,
                            const uint8_t* shard, uint8_t* slabs, hipStream_t s);
+// k_query for a Woodruff key of M bytes (pir_woodruff.h) over the whole domain of 2^n records,
+// one round: the builder waves write each tile's pair products key[a] * key[b] into the LDS ring
+// (wd_tile) while the scan waves stream the shard; then launch_reduce.  The plan is
+// make_query_plan(n, 0, 2, 1, pitch, cus); query_wd_takes says whether its shape is served.
+inline bool query_wd_takes(const QueryPlan& qp) {
+  return (qp.tile == 1024 || qp.tile == 4096) && qp.shape.nq == 1 && !qp.m4r;
+}
+hipError_t launch_query_wd(const QueryPlan& qp, const uint8_t* d_key, uint32_t M, int n,
+                           const uint8_t* shard, uint8_t* slabs, hipStream_t s);
 // XOR the slabs, compact pitch -> record_bytes: d_out[a*efs + b]; nk queries (slabs of query k
 // grid.x*grid.y*slab_bytes apart, answers nq*efs bytes apart).  nslices > 1 (dividing grid.x):
 // per query, nslices answers over consecutive equal runs of the grid.x slabs, i.e. over equal

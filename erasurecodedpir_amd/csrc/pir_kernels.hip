@@ -19,6 +19,7 @@
 #include "pir_tree.h"
 #include "pir_m4r.h"
 #include "pir_mp.h"
+#include "pir_woodruff.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -1519,8 +1520,40 @@ __device__ __forceinline__ void mp_tile(const Tab& T, const uint8_t* __restrict_
   }
 }
 
+// The coefficients of records [rec0, rec0 + TILE) of a Woodruff key (pir_woodruff.h: key[a] *
+// key[b] for the record's pair (a, b)) into a k_query ring slot, one byte per record (one round),
+// by the first nt threads: a thread takes a run of max(4, TILE / nt) consecutive records, finds
+// the first one's pair with wd_pair, walks the rest, and stores its products four to a dword.
+// The key bytes come from global memory (the key[b] of a run are contiguous, key[a] changes at
+// most once in a run shorter than a triangle row).
+template <int TILE, int NRP>
+__device__ __forceinline__ void wd_tile(const uint8_t* __restrict__ key, uint32_t M,
+                                        uint64_t rec0, uint8_t* ring, int tt, int nt) {
+  static_assert(NRP == 1, "the Woodruff mode answers one round");
+  const int per = TILE / nt > 4 ? TILE / nt : 4;  // TILE and nt are powers of two
+  if (tt >= TILE / per) return;
+  const uint32_t r0 = (uint32_t)tt * (uint32_t)per;
+  WdPair p = wd_pair(M, rec0 + r0);
+  uint32_t pa = p.a, ka = key[p.a];
+  uint32_t* out = reinterpret_cast<uint32_t*>(ring + r0);
+  for (int g = 0; g < per / 4; ++g) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (p.a != pa) {
+        pa = p.a;
+        ka = key[pa];
+      }
+      w |= wd_gf_mul(ka, key[p.b]) << (8 * k);
+      wd_next(M, p);
+    }
+    out[g] = w;
+  }
+}
+
+// MPK: 0 = DPF tree keys, 1 = sqrt(N) DPF keys (mp_tile), 2 = a Woodruff key (wd_tile)
 template <int NQ, int NRP, int VEC, bool UNI, int TW, int TILE, int GYMAX, int RING,
-          int NT = kFusedThreads, bool MPK = false>
+          int NT = kFusedThreads, int MPK = 0>
 __global__ __launch_bounds__(NT) void k_query(
     const uint8_t* __restrict__ raw0, uint32_t key_stride, int nk, int p, int n, int nq,
     int party0, int log_parts, uint64_t prefix, int lr, int lt, int ls,
@@ -1530,7 +1563,9 @@ __global__ __launch_bounds__(NT) void k_query(
     uint32_t efs, uint32_t red_mode, MpLayout mpl, StealArgs stl) {
   // MPK: the queue's keys are sqrt(N) DPF keys of layout mpl (key_stride bytes apart; multiparty
   // or covering design), and the tree waves build each tile's shares with mp_tile instead of a
-  // DPF tree; the scan waves, slabs and reduce are the same
+  // DPF tree; the scan waves, slabs and reduce are the same.  MPK == 2: raw0 is a Woodruff key of
+  // mpl.mu bytes (one key, one round) and the tree waves build each tile's coefficients with
+  // wd_tile; no AES table is loaded
   // out != nullptr: the slabs of each query are reduced in-kernel into out (query k at
   // out + k * nq * efs); else the host launches k_reduce.  red_mode 1: the last workgroup to
   // add to qcnt[k] (zero on entry, left zero) XORs every slab.  Modes 2 and 3 (efs % 4 == 0,
@@ -1564,7 +1599,7 @@ __global__ __launch_bounds__(NT) void k_query(
   static_assert(sizeof(Smem) <= 160 * 1024, "LDS");
   __shared__ Smem sm;
   const uint32_t pm1 = (uint32_t)p - 1;
-  load_tables_n<NT>(sm.tab);
+  if constexpr (MPK != 2) load_tables_n<NT>(sm.tab);
   for (int i = threadIdx.x; i < GYMAX * NQ * GW; i += blockDim.x) (&sm.red[0][0])[i] = 0;
   if constexpr (!MPK) stage_key(raw0, p, n, nq, threadIdx.x, NT, sm.scw, sm.tcw, sm.lastcw);
   if (threadIdx.x == 0) {
@@ -1772,7 +1807,14 @@ __global__ __launch_bounds__(NT) void k_query(
       if (team == (uint32_t)NWV) __syncthreads();
       else group_barrier(&sm.bar, gen, team);
     };
-    if constexpr (MPK) {  // a sqrt(N) DPF key's shares instead of a DPF tree
+    if constexpr (MPK == 2) {  // a Woodruff key's pair products
+      wd_tile<TILE, NRP>(raw, (uint32_t)mpl.mu, ((uint64_t)prefix << (n - log_parts)) + tile_row0(i),
+                         ring, tt, nt);
+      sync();  // every coefficient of tile g is in the ring
+      if (wave == 0) lds_signal(&sm.ready);
+      return;
+    }
+    if constexpr (MPK == 1) {  // a sqrt(N) DPF key's shares instead of a DPF tree
       mp_tile<TILE, NRP>(T, raw, mpl, ((uint64_t)prefix << (n - log_parts)) + tile_row0(i), ring,
                          tt, nt);
       sync();  // every share of tile g is in the ring
@@ -2666,6 +2708,31 @@ hipError_t query_nq_mp(const QueryPlan& qp, const uint8_t* d_key, uint32_t key_s
   return hipGetLastError();
 }
 
+// k_query in its Woodruff mode (MPK == 2): wd_tile builds each tile's coefficients from the M key
+// bytes.  One round; 4 builder waves + 12 scan waves, the split the sqrt(N) DPF mode uses for few
+// seeds a row (a tile's coefficients cost far less than its rows' scan), for records of a wave
+// row or more (uniform) and for smaller ones (per-lane coefficients) alike.
+template <int NQ, int TILE>
+hipError_t query_nq_wd(const QueryPlan& qp, const uint8_t* d_key, uint32_t M, int n,
+                       const uint8_t* shard, uint8_t* slabs, hipStream_t s) {
+  static_assert(NQ == 1, "the Woodruff mode answers one round");
+  constexpr int RING = TILE == 4096 ? 2 : 4;
+  const ScanShape& sh = qp.shape;
+  const char* tp = getenv("PIR_QUERY_TREE_PRIO");  // builder-wave priority as launch_query_mp
+  const uint32_t rm = ((tp ? (uint32_t)atoi(tp) : 3u) & 3u) << 8;
+  MpLayout L{};
+  L.mu = M;
+#define PIR_QWD(UNI, GY, gy)                                                                     \
+  hipLaunchKernelGGL((k_query<1, 1, 4, UNI, 4, TILE, GY, RING, kFusedThreads, 2>),               \
+                     dim3(sh.grid.x), dim3(kFusedThreads), 0, s, d_key, 0u, 1, 2, n, 1, 0, 0,    \
+                     (uint64_t)0, qp.lr, qp.lt, 0, nullptr, nullptr, shard, sh.pitch, sh.cpr, gy, \
+                     slabs, nullptr, nullptr, nullptr, 0u, rm, L, StealArgs{})
+  if (sh.uniform) PIR_QWD(true, 4, sh.grid.y);
+  else PIR_QWD(false, 1, 1u);
+#undef PIR_QWD
+  return hipGetLastError();
+}
+
 // ---- where the k_query instantiations are compiled ---------------------------------------
 // Every (rounds, tile) instance of query_nq / query_nq_mp (each a few k_query kernels) is
 // compiled in one of kQueryParts objects: this file built again with -DPIR_QUERY_PART=k (the
@@ -2674,6 +2741,8 @@ hipError_t query_nq_mp(const QueryPlan& qp, const uint8_t* d_key, uint32_t key_s
 #define PIR_QNQ_ARGS                                                                            \
   (const QueryPlan&, const uint8_t*, uint32_t, int, int, int, int, int, uint64_t, const uint8_t*, \
    uint8_t*, uint8_t*, hipStream_t, uint64_t*, uint8_t*, uint32_t*, uint32_t, uint32_t, StealArgs)
+#define PIR_QWD_ARGS                                                                            \
+  (const QueryPlan&, const uint8_t*, uint32_t, int, const uint8_t*, uint8_t*, hipStream_t)
 #define PIR_QMP_ARGS                                                                            \
   (const QueryPlan&, const uint8_t*, uint32_t, int, const MpLayout&, int, int, uint64_t,         \
    const uint8_t*, uint8_t*, hipStream_t)
@@ -2685,10 +2754,11 @@ hipError_t query_nq_mp(const QueryPlan& qp, const uint8_t* d_key, uint32_t key_s
   X(query_nq, 6, 1024, 6) X(query_nq, 7, 1024, 6) X(query_nq, 8, 1024, 6)                        \
   X(query_nq_mp, 1, 4096, 7) X(query_nq_mp, 2, 4096, 7) X(query_nq_mp, 1, 1024, 7)               \
   X(query_nq_mp, 2, 1024, 7) X(query_nq_mp, 3, 1024, 2) X(query_nq_mp, 4, 1024, 1)              \
-  X(query_nq_mp, 5, 1024, 0)
+  X(query_nq_mp, 5, 1024, 0) X(query_nq_wd, 1, 4096, 3) X(query_nq_wd, 1, 1024, 4)
 constexpr int kQueryParts = 8;
 #define PIR_ARGS_query_nq PIR_QNQ_ARGS
 #define PIR_ARGS_query_nq_mp PIR_QMP_ARGS
+#define PIR_ARGS_query_nq_wd PIR_QWD_ARGS
 #ifdef PIR_QUERY_PART
 static_assert(PIR_QUERY_PART >= 0 && PIR_QUERY_PART < kQueryParts, "PIR_QUERY_PART");
 #define PIR_QI(F, NQ, TL, PART) \
@@ -3125,6 +3195,14 @@ hipError_t launch_query_mp(const QueryPlan& qp, const uint8_t* d_key, uint32_t k
     default: return hipErrorInvalidValue;
   }
 #undef PIR_QM
+}
+
+hipError_t launch_query_wd(const QueryPlan& qp, const uint8_t* d_key, uint32_t M, int n,
+                           const uint8_t* shard, uint8_t* slabs, hipStream_t s) {
+  if (!query_wd_takes(qp) || M < 3 || (1ull << n) > (uint64_t)M * (M - 1) / 2)
+    return hipErrorInvalidValue;
+  if (qp.tile == 4096) return query_nq_wd<1, 4096>(qp, d_key, M, n, shard, slabs, s);
+  return query_nq_wd<1, 1024>(qp, d_key, M, n, shard, slabs, s);
 }
 
 size_t query_steal_bytes(const QueryPlan& qp) {

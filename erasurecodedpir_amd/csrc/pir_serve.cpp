@@ -14,6 +14,13 @@
 //                            Results = NUM_ROUNDS x calcShamirResponseLength bytes -- the XOR of
 //                            the reference's Thread slices, which are honest for a Byzantine
 //                            server too)
+//   WOODRUFF_SEARCH_REQUEST (6)  WoodruffSearchRequest{Key []byte} -> WoodruffSearchResponse{
+//                            Results, ServerLatency, ReceiveTime, SendTime}  (woodruff.go:28-90,
+//                            Mode 5: a key of WOODRUFF_M bytes; the shard is the database (k = 1,
+//                            encoded within files on the GPU); Results = WOODRUFF_M + 1 entries of
+//                            ENCODED_FILE_SIZE_BYTES: entry 0 the value answer, the rest zero
+//                            -- the Go server serves the value mode only and sends
+//                            uninitialised memory there)
 //   MULTIPARTY_SEARCH_REQUEST (3)  MultipartySearchRequest{Key} -> MultipartySearchResponse{
 //                            Results, ServerLatency, ReceiveTime, SendTime}  (multiparty.go:16-103,
 //                            Mode 1: shares of the sqrt(N) DPF key scanned on the GPU)
@@ -66,7 +73,8 @@ namespace {
 enum : uint8_t {  // common.go:147-154
   SETUP_REQUEST = 0, TREE_SEARCH_REQUEST = 1, SHAMIR_SEARCH_REQUEST = 2,
   MULTIPARTY_SEARCH_REQUEST = 3,
-  HOLLANTI_SEARCH_REQUEST = 4, CD732_SEARCH_REQUEST = 5, TEST_REQUEST = 7
+  HOLLANTI_SEARCH_REQUEST = 4, CD732_SEARCH_REQUEST = 5, WOODRUFF_SEARCH_REQUEST = 6,
+  TEST_REQUEST = 7
 };
 
 // ---- msgpack (the subset the protocol uses) ----------------------------------------------
@@ -263,7 +271,8 @@ struct Server {
   // tree key length, multiparty (p, t), NUM_CD_KEYS_NEEDED, Hollanti coefficient-vector length,
   // Shamir key length and bytes per response row (efs elsewhere)
   int mode = -1, nq = 0, efs = 0, key_len = 0, p = 0, t = 0, cd_needed = 0;
-  uint64_t num_files = 0, shamir_key_len = 0, row_len = 0;
+  // Woodruff key length (the response has woodruff_m + 1 rows, only the first computed)
+  uint64_t num_files = 0, shamir_key_len = 0, row_len = 0, woodruff_m = 0;
 };
 Server g;
 
@@ -272,9 +281,11 @@ std::string setup(const MVal& req) {  // server.go:295-331
   const int t = (int)req.get_int("T", 1), k = (int)req.get_int("K", 1), r = (int)req.get_int("R");
   const int b = (int)req.get_int("B"), rho = (int)req.get_int("Rho", 1);
   const int mode = (int)req.get_int("Mode"), mac = (int)req.get_int("CheckMAC");
-  if (mode < 0 || mode > 4)
-    return "only the tree (0), multiparty (1), Shamir (2), Hollanti (3) and covering-design (4) "
-           "modes are served by this engine";
+  if (mode < 0 || mode > 5)
+    return "only the tree (0), multiparty (1), Shamir (2), Hollanti (3), covering-design (4) and "
+           "Woodruff (5) modes are served by this engine";
+  if (mode == 5 && (k != 1 || b != 0 || t < 1)) return "Woodruff mode needs K = 1, B = 0 and T >= 1";
+  if (mode == 5 && log_files > 31) return "Woodruff mode serves at most 2^31 records";
   if (mac != 0) return "CheckMAC setups are outside this engine's scope";
   if (mode == 0 && (t != 1 || b != 0)) return "tree mode needs T = 1 and B = 0";
   if (mode == 1 && t < 1) return "multiparty mode needs T >= 1";
@@ -287,6 +298,7 @@ std::string setup(const MVal& req) {  // server.go:295-331
   g.eng = nullptr;
   g.key_len = 0;
   g.mode = -1;
+  if (mode == 5) WOODRUFF_DERIVATIVE = 0;  // the value mode only, like the Go server
   setSystemParams(log_files, fsz, t, k, r, b, rho, mac, mode);
   if (g.party > NUM_PARTIES) return "this server's party index exceeds NUM_PARTIES";
   const int rounds = mode == 1 ? NUM_RSS_KEYS : (mode == 4 ? NUM_CD_KEYS : NUM_ROUNDS);
@@ -297,15 +309,16 @@ std::string setup(const MVal& req) {  // server.go:295-331
   // the party count only sizes tree-DPF keys (modes 1, 3 and 4 answer other key forms); the
   // party index also selects the encode-across evaluation point gf_pow(party, j) (client.cpp:
   // 84-89), so the encode-across modes keep the server's own (Hollanti passes it explicitly)
-  const bool within = mode == 2 || mode == 3;
+  const bool within = mode == 2 || mode == 3 || mode == 5;
   c.num_parties = within ? 2 : (NUM_PARTIES < 2 ? 2 : NUM_PARTIES);
   c.party_index = within ? 1 : g.party;
   // Shamir: the Hermite rows behind the value rows (pir_engine_answer_shamir)
   c.log_num_records = LOG_NUM_ENCODED_FILES + (mode == 2 ? 1 : 0);
   c.record_bytes = (uint32_t)ENCODED_FILE_SIZE_BYTES;
   c.num_rounds = rounds;
-  // Shamir answers are the Thread slices of shamir.go:88-104: honest either way
-  c.is_byzantine = mode == 2 ? 0 : (g.byzantine || (int)req.get_int("IsByzantine"));
+  // Shamir answers are the Thread slices of shamir.go:88-104: honest either way; so are
+  // Woodruff's (server.cpp:569-616: both branches compute the honest answer)
+  c.is_byzantine = (mode == 2 || mode == 5) ? 0 : (g.byzantine || (int)req.get_int("IsByzantine"));
   if (pir_engine_create(&c, &g.eng) != PIR_OK) return std::string("engine: ") + pir_engine_last_error();
   if (ENCODE_ACROSS) {
     // the synthetic database of client.cpp:16-33, encoded across files on the GPU
@@ -332,6 +345,7 @@ std::string setup(const MVal& req) {  // server.go:295-331
   g.shamir_key_len = mode == 2 ? (uint64_t)calcShamirDPFKeyLength(LOG_NUM_ENCODED_FILES) : 0;
   g.row_len = mode == 2 ? pir_engine_shamir_response_len(LOG_NUM_ENCODED_FILES, (uint32_t)g.efs)
                         : (uint64_t)g.efs;
+  g.woodruff_m = mode == 5 ? (uint64_t)WOODRUFF_M : 0;
   g.key_len = pir_engine_key_len(c.num_parties, c.log_num_records, c.num_rounds);
   return "";
 }
@@ -383,8 +397,8 @@ void handle(SSL* ssl) {
                     std::chrono::steady_clock::now() - t0).count());
     } else if (type == TREE_SEARCH_REQUEST || type == MULTIPARTY_SEARCH_REQUEST ||
                type == HOLLANTI_SEARCH_REQUEST || type == CD732_SEARCH_REQUEST ||
-               type == SHAMIR_SEARCH_REQUEST) {
-      // tree.go:17-101, multiparty.go, hollanti.go, cd732.go, shamir.go
+               type == SHAMIR_SEARCH_REQUEST || type == WOODRUFF_SEARCH_REQUEST) {
+      // tree.go:17-101, multiparty.go, hollanti.go, cd732.go, shamir.go, woodruff.go
       const MVal* key = req.get("Key");
       std::vector<uint8_t> out;
       int nq = 0;  // this answer's shape, read under the lock with the engine
@@ -393,11 +407,14 @@ void handle(SSL* ssl) {
         std::lock_guard<std::mutex> lk(g.mu);
         nq = g.nq;
         efs = (size_t)g.row_len;
-        out.resize((size_t)nq * efs);
+        // Woodruff: WOODRUFF_M + 1 entries, the answer in entry 0 and zeros behind it
+        if (type == WOODRUFF_SEARCH_REQUEST && g.mode == 5) nq = (int)g.woodruff_m + 1;
+        out.assign((size_t)nq * efs, 0);
         const int want = type == TREE_SEARCH_REQUEST ? 0
                          : type == MULTIPARTY_SEARCH_REQUEST ? 1
                          : type == CD732_SEARCH_REQUEST ? 4
-                         : type == SHAMIR_SEARCH_REQUEST ? 2 : 3;
+                         : type == SHAMIR_SEARCH_REQUEST ? 2
+                         : type == WOODRUFF_SEARCH_REQUEST ? 5 : 3;
         int rc = PIR_OK;
         if (!g.eng) {
           err = "query before setup";
@@ -420,6 +437,12 @@ void handle(SSL* ssl) {
           else
             rc = pir_engine_answer_cd(g.eng, (const uint8_t*)key->s.data(), key->s.size(),
                                       g.cd_needed, nq, 0, 1, out.data());
+        } else if (type == WOODRUFF_SEARCH_REQUEST) {  // the Thread slices of woodruff.go:61-76, XORed
+          if (!is_bytes(key) || key->s.size() != g.woodruff_m)
+            err = "bad key";
+          else
+            rc = pir_engine_answer_woodruff(g.eng, (const uint8_t*)key->s.data(), key->s.size(), 0,
+                                            g.num_files, out.data());
         } else if (type == SHAMIR_SEARCH_REQUEST) {  // Key [][]byte: NUM_ROUNDS keys of 2^x + 2^y bytes
           std::vector<const uint8_t*> ptrs;
           if (key && key->kind == MVal::ARR && (int)key->a.size() == nq)

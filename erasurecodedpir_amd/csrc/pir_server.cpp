@@ -52,7 +52,7 @@ int IS_HERMITE = 0;
 int D = 0;
 int MAC_SIZE_BYTES = 32;
 int CHECK_MAC = 0;
-int NUM_RSS_KEYS = 0;  // params.cpp:39-46 defaults (Woodruff mode is not served)
+int NUM_RSS_KEYS = 0;  // params.cpp:39-46 defaults
 int NUM_CD_KEYS = 2;   // params.cpp:368-369: the CD532 counts until a covering design is chosen
 int NUM_CD_KEYS_NEEDED = 4;
 int WOODRUFF_M = 0;
@@ -622,6 +622,7 @@ void hmac_sha256(const uint8_t* key, size_t klen, const uint8_t* msg, size_t mle
 namespace pir_shim {
 
 HermiteEncodeFn g_encode_hermite = nullptr;
+const WoodruffHooks* g_woodruff = nullptr;
 
 void with_engine(server* s, int nq, const std::function<void(pir_engine_t*)>& fn) {
   ShimState* st = state_of(s);
@@ -829,16 +830,26 @@ void setSystemParams(int logNumFiles, int fileSizeBytes, int t, int k, int r, in
             "mode is served after pirEnableShamirMode(1))\n");
     abort();
   }
-  if (mode < 0 || mode > 4) {
+  if (mode < 0 || mode > 5) {
     fprintf(stderr, "pir shim: mode %d is outside the engine's scope (tree = 0, multiparty = 1, "
-            "Shamir = 2 once enabled, Hollanti = 3, covering design = 4)\n", mode);
+            "Shamir = 2 once enabled, Hollanti = 3, covering design = 4, Woodruff = 5)\n", mode);
     abort();
+  }
+  if (mode == 5) {  // params.cpp:448-456
+    if (k != 1) {   // assert(K == 1)
+      fprintf(stderr, "pir shim: the Woodruff mode requires k == 1 (got %d)\n", k);
+      abort();
+    }
+    if (b > 0) {
+      fprintf(stderr, "pir shim: malicious (B > 0) Woodruff setups are outside the engine's scope\n");
+      abort();
+    }
   }
   if (mode == 0 && t != 1) {  // params.cpp:415 assert(T == 1)
     fprintf(stderr, "pir shim: tree mode requires t == 1 (got %d)\n", t);
     abort();
   }
-  if ((mode == 2 || mode == 3) && checkMac) {
+  if ((mode == 2 || mode == 3 || mode == 5) && checkMac) {
     fprintf(stderr, "pir shim: CheckMAC setups are outside the engine's scope\n");
     abort();
   }
@@ -863,10 +874,16 @@ void setSystemParams(int logNumFiles, int fileSizeBytes, int t, int k, int r, in
     } else {
       NUM_PARTIES = T + K + R + 2 * B + g_cd_m;
     }
+  } else if (mode == 5) {
+    // value answers: a degree-2T polynomial through 2T + 1 points; with derivatives each server
+    // gives two conditions: int(ceil(double(2T + 1) / 2)) = T + 1 of them
+    NUM_PARTIES = (WOODRUFF_DERIVATIVE ? T + 1 : 2 * T + 1) + R + 2 * B;
+    WOODRUFF_D = 2;  // params.cpp:621-628
+    WOODRUFF_M = calcWoodruffKeyLength(NUM_PARTIES, R, T, logNumFiles, fileSizeBytes);
   } else {
     NUM_PARTIES = K + R + T + 2 * B + (mode == 1 ? 0 : RHO - 1);
   }
-  ENCODE_ACROSS = (mode == 2 || mode == 3) ? 0 : 1;
+  ENCODE_ACROSS = (mode == 2 || mode == 3 || mode == 5) ? 0 : 1;
   // params.cpp:423-429: ceil((2T + 2K) / 2 + R + 2B + RHO - 1) is the party count above; the
   // reference never clears IS_HERMITE again, here every setup starts from 0 (like M and isRss)
   IS_HERMITE = mode == 2 ? 1 : 0;
@@ -1309,8 +1326,11 @@ void runCDQueryThread(server* s, uint8_t* key, int threadNum, int numThreads, ui
     die("runCDQueryThread");
   for (int a = 0; a < NUM_CD_KEYS; ++a) memcpy(result[a], out.data() + a * efs, efs);
 }
-void runWoodruffQueryThread(server*, uint8_t*, int, int, int, uint8_t**) {
-  out_of_scope("runWoodruffQueryThread", "Woodruff");
+// server.cpp:564-616: answered by pir_server_woodruff.cpp where it is linked
+void runWoodruffQueryThread(server* s, uint8_t* key, int threadNum, int startIndex, int endIndex,
+                            uint8_t** result) {
+  if (!pir_shim::g_woodruff) out_of_scope("runWoodruffQueryThread", "Woodruff");
+  pir_shim::g_woodruff->run_thread(s, key, threadNum, startIndex, endIndex, result);
 }
 
 // client.cpp:16-33 (synthetic DB; MAC tags are outside this engine's scope).  The files share
@@ -1587,12 +1607,60 @@ void genOptShamirDPF(int, uint128_t, int, int, int, uint8_t***, uint8_t***, uint
 void assembleShamirResponses(client*, uint8_t*, uint8_t***, uint8_t*, uint8_t***, uint8_t***) {
   out_of_scope("assembleShamirResponses", "Shamir");
 }
-void genWoodruffVs(int, int, uint8_t**) { out_of_scope("genWoodruffVs", "Woodruff"); }
-void genWoodruffQuery(uint128_t, int, int, int, uint8_t**, uint8_t**) {
-  out_of_scope("genWoodruffQuery", "Woodruff");
+// woodruff.cpp:9-13
+void genWoodruffVs(int t, int m, uint8_t** v) {
+  if (!pir_shim::g_woodruff) out_of_scope("genWoodruffVs", "Woodruff");
+  for (int i = 0; i < t; ++i) memset(v[i], i, (size_t)m);
 }
-void assembleWoodruffResponses(client*, uint8_t*, uint8_t***, uint8_t*, uint8_t**) {
-  out_of_scope("assembleWoodruffResponses", "Woodruff");
+// woodruff.cpp:15-31: key i < p is E_index + sum_k (i + 1)^(k + 1) v[k], E_index the indicator
+// of the record's pair (the reference reads it from MAPPING_INDEX; here it is computed)
+void genWoodruffQuery(uint128_t index, int t, int p, int m, uint8_t** v, uint8_t** key_output) {
+  if (!pir_shim::g_woodruff) out_of_scope("genWoodruffQuery", "Woodruff");
+  uint32_t a = 0, b = 0;
+  if (m != WOODRUFF_M ||
+      pir_shim::g_woodruff->pair((uint32_t)WOODRUFF_M, (uint64_t)index, &a, &b) != PIR_OK) {
+    fprintf(stderr, "pir shim: genWoodruffQuery: no record %llu under a key of %d bytes "
+            "(WOODRUFF_M = %d)\n", (unsigned long long)index, m, WOODRUFF_M);
+    abort();
+  }
+  for (int i = 0; i < p; ++i)
+    for (int j = 0; j < m; ++j) {
+      uint8_t x = ((uint32_t)j == a || (uint32_t)j == b) ? 1 : 0;
+      for (int k = 0; k < t; ++k) x ^= gf_mul_h(gf_pow_h((uint8_t)(i + 1), k + 1), v[k][j]);
+      key_output[i][j] = x;
+    }
+}
+// client.cpp:634-697, the value mode (WOODRUFF_DERIVATIVE = 0, B = 0): per byte, the degree-2T
+// polynomial through the first 2T + 1 responses, at 0.  The evaluation points are the same for
+// every byte, so the Vandermonde system is inverted once.
+void assembleWoodruffResponses(client* c, uint8_t* erasureIndexList, uint8_t*** responses,
+                               uint8_t* output, uint8_t** v) {
+  (void)c; (void)v;
+  if (!pir_shim::g_woodruff) out_of_scope("assembleWoodruffResponses", "Woodruff");
+  if (B > 0 || WOODRUFF_DERIVATIVE) {
+    fprintf(stderr, "pir shim: malicious (B > 0) and derivative Woodruff decoding are outside the "
+            "engine's scope\n");
+    abort();
+  }
+  const int nr = NUM_PARTIES - R, m = WOODRUFF_D * T + 1;
+  if (nr < m) {
+    fprintf(stderr, "pir shim: %d responses for a degree-%d interpolation\n", nr, m - 1);
+    abort();
+  }
+  std::vector<uint8_t> pts((size_t)nr);
+  int curr = 1;
+  for (int j = 0; j < nr; ++j) {
+    while (erasureIndexList[curr - 1] == 0) ++curr;
+    pts[(size_t)j] = (uint8_t)curr++;
+  }
+  const std::vector<uint8_t> inv = vandermonde_inverse(pts.data(), m);
+  std::vector<uint8_t> rec((size_t)FILE_SIZE_BYTES, 0);
+  for (int a = 0; a < ENCODED_FILE_SIZE_BYTES && a < (int)FILE_SIZE_BYTES; ++a) {
+    uint8_t x = 0;
+    for (int j = 0; j < m; ++j) x ^= gf_mul_h(responses[j][0][a], inv[(size_t)j]);
+    rec[(size_t)a] = x;
+  }
+  memcpy(output, rec.data(), (size_t)FILE_SIZE_BYTES);
 }
 
 }  // extern "C"

@@ -26,4 +26,15 @@ using HermiteEncodeFn = int (*)(pir_engine_t*, const uint8_t* const* files, uint
                                 uint32_t file_bytes, int k, int party);
 extern HermiteEncodeFn g_encode_hermite;
 
+// The Woodruff mode (mode 5): runWoodruffQueryThread's answers on the engine (value, or with
+// WOODRUFF_DERIVATIVE the M + 1 derivative answers) and the record -> pair map genWoodruffQuery
+// needs (pir_engine_woodruff_pair), registered by
+// pir_server_woodruff.cpp when it is linked (nullptr otherwise: the Woodruff entry points abort).
+struct WoodruffHooks {
+  void (*run_thread)(server* s, uint8_t* key, int threadNum, int startIndex, int endIndex,
+                     uint8_t** result);
+  int (*pair)(uint32_t m, uint64_t i, uint32_t* a, uint32_t* b);
+};
+extern const WoodruffHooks* g_woodruff;
+
 }  // namespace pir_shim

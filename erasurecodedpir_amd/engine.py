@@ -267,6 +267,54 @@ class Engine:
         check(self._lib.pir_engine_answer_shamir_dev(self._h, d_keys, key_pitch, rec0, nrec,
                                                      d_result, stream), "answer_shamir_dev")
 
+    @property
+    def woodruff_m(self):
+        """The Woodruff key length M of this engine's 2^n records (pir_engine_woodruff_m)."""
+        return woodruff_m(self.n)
+
+    @property
+    def woodruff_fused_tile(self):
+        """Records per tile of the single-launch Woodruff path for this engine's whole domain
+        (0: its shape is not served, every answer takes the coefficient kernel + scan)."""
+        return int(self._lib.pir_engine_woodruff_fused_tile(self._h))
+
+    def answer_woodruff(self, key, rec0=0, nrec=None):
+        """Woodruff value answer (runWoodruffQueryThread, src/c/server.cpp:564-616) of a
+        one-round engine: key is woodruff_m bytes; XOR over the records i of [rec0, rec0 + nrec)
+        of key[a_i] * key[b_i] * row_i, (a_i, b_i) the i-th 2-subset of [0, M).
+        -> (record_bytes,) uint8."""
+        k = np.ascontiguousarray(np.asarray(key, np.uint8).reshape(-1))
+        nrec = self.num_rows - rec0 if nrec is None else nrec
+        out = np.empty(self.record_bytes, np.uint8)
+        check(self._lib.pir_engine_answer_woodruff(self._h, k.ctypes.data_as(ctypes.c_void_p),
+                                                   k.size, rec0, nrec,
+                                                   out.ctypes.data_as(ctypes.c_void_p)),
+              "pir_engine_answer_woodruff")
+        return out
+
+    def answer_woodruff_deriv(self, key, rec0=0, nrec=None):
+        """Woodruff derivative answers (WOODRUFF_DERIVATIVE = 1, server.cpp:618-644):
+        -> (woodruff_m + 1, record_bytes): the value answer, then for j < M the XOR over the
+        records whose pair holds j of key[the pair's other index] * row."""
+        k = np.ascontiguousarray(np.asarray(key, np.uint8).reshape(-1))
+        nrec = self.num_rows - rec0 if nrec is None else nrec
+        out = np.empty((k.size + 1, self.record_bytes), np.uint8)
+        check(self._lib.pir_engine_answer_woodruff_deriv(self._h,
+                                                         k.ctypes.data_as(ctypes.c_void_p),
+                                                         k.size, rec0, nrec,
+                                                         out.ctypes.data_as(ctypes.c_void_p)),
+              "pir_engine_answer_woodruff_deriv")
+        return out
+
+    def answer_woodruff_deriv_dev(self, d_key, key_len, rec0, nrec, d_result, stream=None):
+        check(self._lib.pir_engine_answer_woodruff_deriv_dev(self._h, d_key, key_len, rec0, nrec,
+                                                             d_result, stream),
+              "answer_woodruff_deriv_dev")
+
+    def answer_woodruff_dev(self, d_key, key_len, rec0, nrec, d_result, stream=None):
+        check(self._lib.pir_engine_answer_woodruff_dev(self._h, d_key, key_len, rec0, nrec,
+                                                       d_result, stream), "answer_woodruff_dev")
+
     def answer_mp(self, key, p, t, thread_num=0, num_threads=1):
         """Multiparty sqrt(N) DPF answer (runOptimizedMultiPartyDPFQuery[Thread], src/c/
         server.cpp:136-176, :384-430): the key's NUM_RSS_KEYS shares of every record (the
@@ -441,6 +489,19 @@ class Engine:
 def shamir_response_len(log_domain, record_bytes):
     """calcShamirResponseLength: (2^x + 2^y + 2) * record_bytes, x = ceil(n/2), y = n - x."""
     return int(_lib.load().pir_engine_shamir_response_len(log_domain, record_bytes))
+
+
+def woodruff_m(log_num_records):
+    """WOODRUFF_M: the smallest M >= 3 with M (M - 1) / 2 >= 2^n (params.cpp:621-628); host only."""
+    return int(_lib.load().pir_engine_woodruff_m(log_num_records))
+
+
+def woodruff_pair(m, i):
+    """The i-th 2-subset (a, b), a < b, of [0, m) in lexicographic order; host only."""
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    check(_lib.load().pir_engine_woodruff_pair(m, i, ctypes.byref(a), ctypes.byref(b)),
+          "pir_engine_woodruff_pair")
+    return a.value, b.value
 
 
 def mp_num_keys(p, t):

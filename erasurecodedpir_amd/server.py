@@ -198,6 +198,21 @@ class Server:
                                    threadNum, numThreads, _row_ptrs(out))
         return out
 
+    def runWoodruffQueryThread(self, key, threadNum, startIndex, endIndex):
+        """Woodruff value answer over the records [startIndex, endIndex) (server.cpp:564-616)
+        under setSystemParams(mode 5): key = WOODRUFF_M bytes -> (1, EFS), or with
+        WOODRUFF_DERIVATIVE set (WOODRUFF_M + 1, EFS): the value answer and the M derivative
+        answers (server.cpp:618-644)."""
+        m = _lib.global_int("WOODRUFF_M")
+        k = np.frombuffer(bytes(key), np.uint8).copy()
+        if k.size != m:  # the shim reads WOODRUFF_M bytes
+            raise ValueError(f"Woodruff key of {k.size} bytes, expected {m}")
+        nout = m + 1 if _lib.global_int("WOODRUFF_DERIVATIVE") else 1
+        out = np.zeros((nout, _lib.global_int("ENCODED_FILE_SIZE_BYTES")), np.uint8)
+        self._lib.runWoodruffQueryThread(ctypes.byref(self.s), k.ctypes.data_as(ctypes.c_void_p),
+                                         threadNum, startIndex, endIndex, _row_ptrs(out))
+        return out
+
     def freeServer(self):
         """Returns once the server is unreachable; the engine teardown runs in the background
         (pirServerWaitFreed / wait_freed() waits for it)."""
@@ -240,6 +255,11 @@ def assembleShamirQueryThreadResults(server, parts):
     """parts: (numThreads, NUM_ROUNDS, response_len) -> (NUM_ROUNDS, response_len)
     (server.cpp:304-319)."""
     return _assemble("assembleShamirQueryThreadResults", server, parts)
+
+
+def assembleWoodruffQueryThreadResults(server, parts):
+    """parts: (numThreads, 1 or WOODRUFF_M + 1, EFS) -> their XOR (server.cpp:647-665)."""
+    return _assemble("assembleWoodruffQueryThreadResults", server, parts)
 
 
 def assembleMultipartyDPFQueryThreadResults(server, parts):
@@ -380,4 +400,50 @@ def assembleHollantiResponses(erasure, responses, c=None):
     cl = c if c is not None else CClient()
     lib.assembleHollantiResponses(ctypes.byref(cl), er.ctypes.data_as(ctypes.c_void_p), outer,
                                   out.ctypes.data_as(ctypes.c_void_p))
+    return out
+
+
+def set_woodruff_derivative(on):
+    """WOODRUFF_DERIVATIVE (params.h:41), read by setSystemParams(mode 5) for NUM_PARTIES and
+    by runWoodruffQueryThread for the answer's shape."""
+    ctypes.c_int.in_dll(_lib.load(), "WOODRUFF_DERIVATIVE").value = int(bool(on))
+
+
+def genWoodruffVs(t, m):
+    """woodruff.cpp:9-13: the t masking vectors of m bytes (v[i] = m bytes of value i)."""
+    v = np.zeros((t, m), np.uint8)
+    _lib.load().genWoodruffVs(t, m, ctypes.cast(_row_ptrs(v), ctypes.c_void_p))
+    return v
+
+
+def genWoodruffQuery(index, t, p, m, v):
+    """woodruff.cpp:15-31 under setSystemParams(mode 5): the p keys of m = WOODRUFF_M bytes for
+    record `index`, key i = E_index + sum_k (i + 1)^(k + 1) v[k] over GF(2^8)."""
+    v = np.ascontiguousarray(np.asarray(v, np.uint8).reshape(t, m))
+    keys = np.zeros((p, m), np.uint8)
+    idx = _lib.U128(int(index) & (2 ** 64 - 1), int(index) >> 64)
+    _lib.load().genWoodruffQuery(idx, t, p, m, ctypes.cast(_row_ptrs(v), ctypes.c_void_p),
+                                 ctypes.cast(_row_ptrs(keys), ctypes.c_void_p))
+    return keys
+
+
+def assembleWoodruffResponses(erasure, responses, v=None, c=None):
+    """Client decode of one value-mode Woodruff query (client.cpp:634-697) under the current
+    setSystemParams(mode 5): responses = [NUM_PARTIES - R][1][EFS] from the servers with
+    erasure[q-1] = 1, in increasing q.  Returns the FILE_SIZE_BYTES record."""
+    lib = _lib.load()
+    prm = params()
+    nr, efs = prm["NUM_PARTIES"] - prm["R"], prm["ENCODED_FILE_SIZE_BYTES"]
+    resp = np.ascontiguousarray(np.asarray(responses, np.uint8).reshape(nr, 1, efs))
+    er = np.ascontiguousarray(np.asarray(erasure, np.uint8))
+    rows = [(c_u8_p * 1)(resp[j, 0].ctypes.data_as(c_u8_p)) for j in range(nr)]
+    outer = (ctypes.POINTER(c_u8_p) * nr)(*[ctypes.cast(r, ctypes.POINTER(c_u8_p)) for r in rows])
+    out = np.zeros(_lib.global_int("FILE_SIZE_BYTES"), np.uint8)
+    vp = None
+    if v is not None:
+        v = np.ascontiguousarray(np.asarray(v, np.uint8))
+        vp = ctypes.cast(_row_ptrs(v), ctypes.c_void_p)
+    cl = c if c is not None else CClient()
+    lib.assembleWoodruffResponses(ctypes.byref(cl), er.ctypes.data_as(ctypes.c_void_p), outer,
+                                  out.ctypes.data_as(ctypes.c_void_p), vp)
     return out

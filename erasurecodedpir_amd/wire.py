@@ -18,6 +18,7 @@ import numpy as np
 SETUP_REQUEST, TREE_SEARCH_REQUEST, MULTIPARTY_SEARCH_REQUEST, HOLLANTI_SEARCH_REQUEST = 0, 1, 3, 4
 CD732_SEARCH_REQUEST, TEST_REQUEST = 5, 7
 SHAMIR_SEARCH_REQUEST = 2
+WOODRUFF_SEARCH_REQUEST = 6
 
 
 class WireError(RuntimeError):
@@ -72,7 +73,7 @@ class Conn:
 def setup(addr, log_num_files, file_size_bytes, k, r, rho=1, num_threads=1, is_byzantine=0,
           mode=0, t=1, b=0):
     """SETUP_REQUEST with the fields of common.go:51-65 (no MAC): mode 0 tree, 1 multiparty,
-    2 Shamir, 3 Hollanti, 4 covering design."""
+    2 Shamir, 3 Hollanti, 4 covering design, 5 Woodruff (k = 1)."""
     host, port = addr
     req = {"BenchmarkDir": "", "LogNumFiles": log_num_files, "FileSizeBytes": file_size_bytes,
            "T": t, "K": k, "R": r, "B": b, "Rho": rho, "Mode": mode, "IsByzantine": is_byzantine,
@@ -115,6 +116,15 @@ def shamir_query(addr, keys):
     host, port = addr
     with Conn(host, port) as c:
         return c.call(SHAMIR_SEARCH_REQUEST, {"Key": [bytes(np.asarray(k, np.uint8)) for k in keys]})
+
+
+def woodruff_query(addr, key):
+    """WOODRUFF_SEARCH_REQUEST (server_util/woodruff.go:28-90): key = WOODRUFF_M bytes; Results =
+    WOODRUFF_M + 1 entries of ENCODED_FILE_SIZE_BYTES, entry 0 the value answer and the rest zero
+    (the server process serves the value mode only)."""
+    host, port = addr
+    with Conn(host, port) as c:
+        return c.call(WOODRUFF_SEARCH_REQUEST, {"Key": bytes(np.asarray(key, np.uint8))})
 
 
 def tree_query(addrs, index, log_num_files, file_size_bytes, k, r, rho=1, device=0):

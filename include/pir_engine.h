@@ -20,6 +20,10 @@
  *   pir_engine_answer_shamir[_dev]   runOptShamirDPFQuery / ...Thread       server.cpp:203-302
  *   pir_engine_encode_hermite_*      generate_hermite_within_file           client.cpp:57-68
  *   pir_engine_shamir_response_len   calcShamirResponseLength               utils.cpp:140-143
+ *   pir_engine_answer_woodruff[_dev] runWoodruffQueryThread (value answer)  server.cpp:564-616
+ *   pir_engine_answer_woodruff_deriv[_dev]  ... with WOODRUFF_DERIVATIVE    server.cpp:618-644
+ *   pir_engine_woodruff_m            calcWoodruffKeyLength / WOODRUFF_M     params.cpp:621-628
+ *   pir_engine_woodruff_pair         makeCombi(M, 2)[i] - 1                 params.cpp:629-640
  *   pir_engine_answer_mp[_dev]       runOptimizedMultiPartyDPFQuery[Thread] server.cpp:136-176,
  *                                    (evalAllOptMultiPartyDPF[Thread])      :384-430,
  *                                                                 multiparty_dpf.cpp:467-615
@@ -183,6 +187,39 @@ int pir_engine_encode_hermite_dev(pir_engine_t *e, const uint8_t *d_files, uint6
                                   uint64_t num_files, uint32_t file_bytes, int k, int party);
 int pir_engine_encode_hermite_rows(pir_engine_t *e, const uint8_t *const *files,
                                    uint64_t num_files, uint32_t file_bytes, int k, int party);
+/* ---- Woodruff mode (runWoodruffQueryThread, server.cpp:564-616, WOODRUFF_D = 2) ----
+ * A Woodruff engine has num_rounds = 1, no partitions and no communicator; its N = 2^n rows are
+ * the records.  The key is M bytes, M the smallest integer >= 3 with M (M - 1) / 2 >= N
+ * (pir_engine_woodruff_m; 0 for n outside [0, 31]).  Record i belongs to the i-th pair (a, b),
+ * 0 <= a < b < M, in lexicographic order (pir_engine_woodruff_pair, exact for every i < 2^32:
+ * start(a) = a (2M - a - 1) / 2 <= i < start(a + 1), b = a + 1 + i - start(a)); pairs of rank
+ * >= N are unused.  The value answer over the records [rec0, rec0 + nrec) (the Thread form's
+ * [startIndex, endIndex); partial answers XOR to the whole), over GF(2^8)/0x11d:
+ *     result = XOR_i key[a_i] * key[b_i] * row_i                   (record_bytes bytes)
+ * The derivative answers (WOODRUFF_DERIVATIVE = 1, server.cpp:618-644) are M + 1 records of
+ * record_bytes bytes:
+ *     result[0]     = the value answer
+ *     result[1 + j] = XOR_{i : j in {a_i, b_i}} key[the other index] * row_i,   j < M
+ * All M + 1 are overwritten (the reference zeroes only the first and XORs into whatever the
+ * caller's other M buffers held).  Two passes over the shard.
+ * isByzantine changes nothing in the reference (both branches are the same) and nothing here.
+ * Both helpers are host only and need no GPU. */
+uint32_t pir_engine_woodruff_m(int log_num_records);
+int pir_engine_woodruff_pair(uint32_t m, uint64_t i, uint32_t *a, uint32_t *b);
+int pir_engine_answer_woodruff(pir_engine_t *e, const uint8_t *key, uint64_t key_len,
+                               uint64_t rec0, uint64_t nrec, uint8_t *result);
+/* device form: key and result in device memory (any alignment); asynchronous on `stream` */
+int pir_engine_answer_woodruff_dev(pir_engine_t *e, const uint8_t *d_key, uint64_t key_len,
+                                   uint64_t rec0, uint64_t nrec, uint8_t *d_result, void *stream);
+int pir_engine_answer_woodruff_deriv(pir_engine_t *e, const uint8_t *key, uint64_t key_len,
+                                     uint64_t rec0, uint64_t nrec, uint8_t *result);
+int pir_engine_answer_woodruff_deriv_dev(pir_engine_t *e, const uint8_t *d_key, uint64_t key_len,
+                                         uint64_t rec0, uint64_t nrec, uint8_t *d_result,
+                                         void *stream);
+/* the tile (records) of the single-launch path that answers this engine's whole domain when
+ * $PIR_WD_FUSED selects it (k_query's Woodruff mode), 0 where its shape is not served and every
+ * answer goes through the coefficient kernel + scan */
+int pir_engine_woodruff_fused_tile(pir_engine_t *e);
 /* Multiparty sqrt(N) DPF answer of party index 1..p with threshold t (the engine must have
  * num_rounds == pir_engine_mp_num_keys(p, t), one output share per round):
  *   result[a] = XOR_{r in rows} share[a][r] * shard row r,   a < NUM_RSS_KEYS,
@@ -274,7 +311,10 @@ int pir_engine_memcpy_d2h(pir_engine_t *e, void *h_dst, const void *d_src, size_
  * slot read by its own path and reported under the newest answer's phase names, fills up to
  * `max` {name, ms} pairs and returns the count.  A Shamir answer (fused = 4) reports k_query's
  * phase names: launch = start -> the response zeroed, scan = the rows pass, the strips pass and
- * the Hermite scan, reduce = the Hermite slabs' k_reduce + the totals kernel. */
+ * the Hermite scan, reduce = the Hermite slabs' k_reduce + the totals kernel.  A Woodruff answer
+ * (fused = 5: the single launch, 6: coefficient kernel + scan) reports them too: launch = start
+ * -> the first kernel, scan = that kernel (6: both kernels), reduce = k_reduce; its derivative
+ * answers (fused = 7): launch = start -> the answer zeroed, scan = the two passes, reduce = 0. */
 typedef struct {
     char name[32];
     float ms;

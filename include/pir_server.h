@@ -35,7 +35,10 @@
  *   - every setSystemParams starts from the covering designs' M = 4 and isRss = 1
  *     (params.cpp:12, :372): the reference keeps the M = 2 of a K = 2, B = 1 CD setup
  *     (params.cpp:440) and a cleared isRss (:520-599) for all later calls;
- *   - no Woodruff MAPPING_INDEX tables (params.cpp:621-640; out of scope, and overflowing).
+ *   - no Woodruff MAPPING_INDEX tables (params.cpp:621-640: NUM_FILES rows of 2 bytes that hold
+ *     8): record i's pair is computed where it is needed (pir_engine_woodruff_pair);
+ *   - WOODRUFF_M / WOODRUFF_D are set by a mode-5 setup only (the reference sets them, and builds
+ *     the tables, in every mode).
  *
  * Setup (src/server/server.go:299-331: setSystemParams, initialize_client, initializeServer,
  * encode_*_files_server): the encode runs on the GPU from the client's host files and leaves the
@@ -122,7 +125,8 @@ extern int CHECK_MAC;
 /* globals of the other PIR modes (params.h:39-54), read by the Go mode handlers
  * (src/server_util/{multiparty,cd732,woodruff}.go); NUM_RSS_KEYS = the multiparty answer's
  * share count (params.cpp:603-619), NUM_CD_KEYS the covering-design answer's (params.cpp:519-599);
- * the Shamir and Woodruff modes are not served (see below) */
+ * WOODRUFF_M = the Woodruff key length of a mode-5 setup, WOODRUFF_DERIVATIVE (set by the caller
+ * before setSystemParams) selects the derivative answers and their party count */
 extern int NUM_RSS_KEYS;
 extern int NUM_CD_KEYS;
 extern int WOODRUFF_M;
@@ -189,10 +193,18 @@ void pirEnableShamirMode(int on);
 void runOptShamirDPFQuery(server *s, uint8_t **keys, uint8_t **result);
 void runOptShamirDPFQueryThread(server *s, uint8_t **keys, int threadNum, int startIndex,
                                 int endIndex, uint8_t **result);
-/* ---- the Woodruff mode's server entry point, bound by src/server_util/woodruff.go:69.  The
- *      mode is outside this engine's scope: setSystemParams refuses modes 5, 6, and this aborts
- *      with a message if reached anyway.  The assemble functions are the reference's XOR folds
- *      (server.cpp:304-319, 647-665). ---- */
+/* ---- Woodruff PIR (mode 5, src/server_util/woodruff.go:69): runWoodruffQueryThread
+ *      (server.cpp:564-645) on the engine (pir_engine_answer_woodruff[_deriv]).  setSystemParams
+ *      mode 5 sizes as params.cpp:448-456 (K == 1; NUM_PARTIES = 2T + 1 + R + 2B, or
+ *      ceil((2T + 1) / 2) + R + 2B with WOODRUFF_DERIVATIVE set before the call; ENCODE_ACROSS =
+ *      0; WOODRUFF_D = 2, WOODRUFF_M = calcWoodruffKeyLength); CheckMAC and B > 0 are refused.
+ *      key = WOODRUFF_M bytes; result[0] = the value answer over the records [startIndex,
+ *      endIndex), ENCODED_FILE_SIZE_BYTES bytes; with WOODRUFF_DERIVATIVE, result[1 + j], j <
+ *      WOODRUFF_M, the derivative answers -- all WOODRUFF_M + 1 buffers are overwritten (the
+ *      reference zeroes only result[0] and XORs into whatever the others held).  isByzantine
+ *      changes nothing (both branches of the reference are the same).  The assemble functions
+ *      are the reference's XOR folds (server.cpp:304-319, 647-665).  Mode 6 (Goldberg) stays
+ *      refused. ---- */
 void runWoodruffQueryThread(server *s, uint8_t *key, int threadNum, int startIndex, int endIndex,
                             uint8_t **result);
 void assembleShamirQueryThreadResults(server *s, uint8_t ***in, int numThreads, uint8_t **out);
@@ -245,8 +257,11 @@ int calcCDDPFKeyLength(int p, int log_domainSize, int t, int num_cd_keys_needed,
 int calcWoodruffKeyLength(int p, int r, int t, int logDomainSize,
                           int fileSizeBytes); /* utils.cpp:145-153 */
 /* The other modes' client halves (multiparty key generation and decode, CD key generation and
- * decode, Shamir, Woodruff): outside the server path this engine replaces; these abort with a
- * message. */
+ * decode, Shamir): outside the server path this engine replaces; these abort with a message.
+ * The Woodruff three are served for the value mode: genWoodruffVs (woodruff.cpp:9-13, the
+ * reference's memset(v[i], i, m)), genWoodruffQuery (woodruff.cpp:15-31, m == WOODRUFF_M) and
+ * assembleWoodruffResponses (client.cpp:634-697 with WOODRUFF_DERIVATIVE = 0 and B = 0: per
+ * byte the degree-2T interpolation at 0; the derivative decode aborts with a message). */
 void generateMultiPartyDPFQuery(client *c, int index, uint8_t ***keys);
 void assembleMultiPartyResponses(client *c, uint8_t *erasureIndexList, uint8_t ***responses,
                                  uint8_t *output);

@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Woodruff answers against one shard-sized read, on one GPU.
+
+One engine of 2^n records (default 2^24 x 1 KiB: 16 GiB), HIP events around the device forms
+after warm-up, four legs alternated in the same process so that all see the same machine state:
+
+  fused    pir_engine_answer_woodruff_dev with $PIR_WD_FUSED=2: k_query's Woodruff mode (the
+           pair products built into the LDS ring beside the scan) + k_reduce
+  two      the same with $PIR_WD_FUSED=0: k_woodruff_coefs, k_scan_uni, k_reduce
+  coefs    pir_engine_answer_coefs_dev, one round over the same rows: the interleave kernel,
+           k_scan_uni, k_reduce -- one shard-sized read of the explicit-coefficient scan
+  deriv    pir_engine_answer_woodruff_deriv_dev: the rows pass, the totals kernel, the columns
+           pass (two shard-sized reads)
+
+Prints ONE JSON line: per leg the median, min and max ms, each leg's spread (max - min), the
+fused leg against the other two, and the derivative answer as a multiple of the coefs leg.  The
+fused path is worth being the default only if it is no slower than `two` and `coefs` by more than
+the spread the run shows between repeats of one leg.
+
+    python tools/bench_woodruff.py [--log-records 24] [--record-bytes 1024] [--iters 10]
+                                   [--warmup 3] [--no-deriv]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import erasurecodedpir_amd as pir  # noqa: E402
+from bench_shamir import Events, hip_runtime  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log-records", type=int, default=24)
+    ap.add_argument("--record-bytes", type=int, default=1024)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-deriv", action="store_true")
+    a = ap.parse_args()
+    n, efs = a.log_records, a.record_bytes
+    N, M = 1 << n, pir.woodruff_m(n)
+    ev = Events(hip_runtime())
+    rng = np.random.default_rng(5)
+    with pir.Engine(2, 1, n, efs, 1) as e:
+        e.fill_shard_random(15)
+        tile = e.woodruff_fused_tile
+        d_key, d_res = e.alloc_dev(M), e.alloc_dev((M + 1) * efs)
+        d_coefs = e.alloc_dev(N)
+        e.h2d(d_key, rng.integers(0, 256, M, dtype=np.uint8))
+        e.h2d(d_coefs, rng.integers(0, 256, N, dtype=np.uint8))
+
+        def forced(mode):
+            def run():
+                os.environ["PIR_WD_FUSED"] = mode   # read per answer
+                e.answer_woodruff_dev(d_key, M, 0, N, d_res)
+            return run
+
+        legs = {"two": forced("0"),
+                "coefs": lambda: e.answer_coefs_dev(d_coefs, N, 0, N, d_res)}
+        if tile:
+            legs["fused"] = forced("2")
+        if not a.no_deriv:
+            legs["deriv"] = lambda: e.answer_woodruff_deriv_dev(d_key, M, 0, N, d_res)
+        # the two value paths give the same bytes
+        same = None
+        if tile:
+            legs["fused"]()
+            r_f = e.d2h(d_res, efs).copy()
+            legs["two"]()
+            same = bool(np.array_equal(r_f, e.d2h(d_res, efs)))
+        for _ in range(a.warmup):
+            for fn in legs.values():
+                fn()
+        e.sync()
+        ms = {k: [] for k in legs}
+        for _ in range(a.iters):
+            for k, fn in legs.items():
+                ms[k].append(ev.time(e.stream, fn))
+        os.environ.pop("PIR_WD_FUSED", None)
+    out = {"bench": "woodruff", "log_records": n, "record_bytes": efs, "key_len": M,
+           "fused_tile": tile, "fused_equals_two_kernel": same, "iters": a.iters,
+           "warmup": a.warmup, "shard_bytes": N * efs, "legs": {}}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        out["legs"][k] = {"ms": round(med, 4), "ms_min": round(min(v), 4),
+                          "ms_max": round(max(v), 4), "spread": round(max(v) - min(v), 4),
+                          "gbps_of_NEFS": round(N * efs / med / 1e6, 1)}
+    L = out["legs"]
+    if "fused" in L:
+        spread = max(x["spread"] for x in L.values() if x is not L.get("deriv"))
+        out["fused_minus_two_ms"] = round(L["fused"]["ms"] - L["two"]["ms"], 4)
+        out["fused_minus_coefs_ms"] = round(L["fused"]["ms"] - L["coefs"]["ms"], 4)
+        out["value_legs_spread_ms"] = spread
+        out["fused_no_slower"] = bool(L["fused"]["ms"] <= min(L["two"]["ms"], L["coefs"]["ms"])
+                                      + spread)
+    if "deriv" in L:
+        out["deriv_over_coefs"] = round(L["deriv"]["ms"] / L["coefs"]["ms"], 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
