@@ -109,6 +109,9 @@ PROTOTYPES = {
     "pir_engine_woodruff_fused_tile": (_I, [_P]),
     "pir_engine_answer_woodruff": (_I, [_P, _P, _U64, _U64, _U64, _P]),
     "pir_engine_answer_woodruff_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
+    "pir_engine_answer_woodruff_queue": (_I, [_P, _P, _U64, _I, _U64, _U64, _P]),
+    "pir_engine_answer_woodruff_queue_dev": (_I, [_P, _P, _U64, _I, _U64, _U64, _P, _P]),
+    "pir_engine_reserve_woodruff_queue": (_I, [_P, _I]),
     "pir_engine_answer_woodruff_deriv": (_I, [_P, _P, _U64, _U64, _U64, _P]),
     "pir_engine_answer_woodruff_deriv_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
     "pir_engine_answer_mp": (_I, [_P, _P, _U64, _I, _I, _I, _I, _P]),

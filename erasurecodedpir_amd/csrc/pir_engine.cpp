@@ -142,6 +142,8 @@ struct pir_engine {
   int stream_share = 1;         // $PIR_STREAM_SHARE: 0 never, 1 stream_share_policy, 2 wherever supported
   int stream_group = 0;         // $PIR_STREAM_G: keys per pass of a shared queue (0: the policy's)
   bool stream_narrow = false;   // $PIR_STREAM_NARROW=1: narrower scans for short groups (diagnostics)
+  int wd_share = 1;             // $PIR_WD_SHARE: 0 never, 1 woodruff_share_policy, 2 every queue of >= 2
+  int wd_group = 0;             // $PIR_WD_G: keys per pass of a shared Woodruff queue (0: 8)
   int batch_scan_bpc = 2;       // scan workgroups per CU in batched answers ($PIR_BATCH_SCAN_BPC)
   int batch_k_last = -1;        // levels of the batched leaf stage (-1: make_plan's; $PIR_BATCH_KLAST)
   uint8_t* d_result = nullptr;  // nq*efs (host-API staging)
@@ -709,7 +711,8 @@ constexpr int kNumPhases = 9;
 // A Woodruff answer (fused == 5: k_query's Woodruff mode, 6: k_woodruff_coefs + the scan) too:
 // "launch" = answer start -> its first kernel, "scan" = that kernel (with 6, both), "reduce" =
 // k_reduce; its derivative answers (fused == 7): "launch" = start -> the answer zeroed, "scan" =
-// the rows pass, the totals kernel and the columns pass, "reduce" = 0
+// the rows pass, the totals kernel and the columns pass, "reduce" = 0; a shared Woodruff queue
+// (fused == 8): answer_woodruff_queue_locked
 const char* const kQueryPhaseNames[] = {"launch", "scan", "reduce", "comm_fold", "total", "fused"};
 constexpr int kNumQueryPhases = 6;
 
@@ -1147,6 +1150,124 @@ int check_woodruff(const pir_engine* e, uint64_t key_len, uint64_t rec0, uint64_
   return PIR_OK;
 }
 
+// Keys per shard pass of a queue of nk Woodruff value queries by default; 0: every key its own
+// answer (answer_woodruff_locked), back to back.  A pure function of the shape, on only for the
+// families where the shared queue measured faster than the parent build's back-to-back single
+// answers by more than the largest spread of any leg of that run (tools/bench_woodruff.py
+// --queue, profiles/woodruff_queue/README.md); a family nobody measured stays off.
+int woodruff_share_policy(uint32_t pitch, uint64_t rows, int nk) {
+  // measured: queues of 2, 4, 8 and 20 keys over 2^20 and 2^24 rows of 1 KiB, 2^24 of 256 B and
+  // 2^22 of 2 KiB, 8 keys per pass.  4 keys and more: 1.9-2.3x the parent at 4, 3.8-4.6x at 8,
+  // 3.3-3.8x at 20 (7 + 7 + 6), on every shape.  2 keys: 1.0-1.19x, inside the spread on three
+  // of the four shapes (a pass of 8 key slots costs 1.8 single answers), so they stay unshared
+  if (nk < 4) return 0;
+  const bool measured = (pitch == 1024 && rows >= (1ull << 20)) ||
+                        (pitch == 256 && rows >= (1ull << 24)) ||
+                        (pitch == 2048 && rows >= (1ull << 22));
+  return measured ? 8 : 0;
+}
+
+// the group size of a Woodruff queue of nk keys (0: unshared).  $PIR_WD_SHARE: 0 never shares, 1
+// (default) follows woodruff_share_policy, 2 shares every queue of two or more keys (every shape
+// has a group scan: one round, so at most 8 rounds per pass); $PIR_WD_G overrides the group size
+int woodruff_group(const pir_engine* e, int nk) {
+  if (e->wd_share == 0 || nk < 2) return 0;
+  int g = woodruff_share_policy(e->pitch, e->rows, nk);
+  if (g == 0 && e->wd_share < 2) return 0;
+  if (g == 0) g = 8;
+  return e->wd_group > 0 ? e->wd_group : g;
+}
+
+// a group of G key slots over nrec records: record-major shares (the coefficient kernel writes
+// all of a record's bytes at once), whichever scan takes them
+pir::ScanShape woodruff_group_shape(const pir_engine* e, uint64_t nrec, int G) {
+  bool kmaj = false;
+  pir::ScanShape sh = group_scan_shape(e, nrec, G, G, &kmaj);
+  sh.ckey = 0;
+  sh.ckoff = 0;
+  return sh;
+}
+
+size_t wd_share_bytes(uint64_t nrec, int W) { return ((size_t)nrec * W + 15) & ~(size_t)15; }
+
+// every buffer a Woodruff queue of up to nk keys over up to nrec records touches, shared or not
+int ensure_woodruff_queue(pir_engine* e, uint32_t M, int nk, uint64_t nrec) {
+  const auto& c = e->cfg;
+  pir::ScanShape sh = pir::make_scan_shape(std::max<uint64_t>(nrec, 1), e->pitch, 1, e->num_cus);
+  size_t slab = (size_t)sh.grid.x * sh.grid.y * sh.slab_bytes;
+  pir::QueryPlan qp{};
+  if (woodruff_fused_takes(e, &qp)) slab = std::max(slab, pir::query_slab_bytes(qp));
+  int rc = PIR_OK;
+  if (const int G = nrec ? woodruff_group(e, nk) : 0) {
+    sh = woodruff_group_shape(e, nrec, G);
+    slab = std::max(slab, (size_t)sh.grid.x * sh.grid.y * sh.slab_bytes);
+    // the share buffer, then the interleaved key table of the shapes whose table outgrows LDS
+    rc = ensure_buf(&e->d_cb, &e->cb_cap, wd_share_bytes(nrec, sh.nrp) + (size_t)M * sh.nrp);
+    if (!rc && !e->d_gtmp) HIP_TRY(hipMalloc(&e->d_gtmp, (size_t)16 * c.record_bytes));
+  }
+  if (!rc) rc = ensure_slabs(e, slab);
+  return rc;
+}
+
+// A queue of nk Woodruff value queries over the records [rec0, rec0 + nrec): d_keys nk x M bytes,
+// d_result nk x efs, result k what answer_woodruff_locked gives for key k.  Shared (woodruff_group
+// > 0): the keys go into ceil(nk / G) groups of as equal sizes as possible, as answer_batch_core's
+// queue does, and every group takes one full-width pass, all on s: launch_woodruff_coefs_g into
+// the share buffer, the G-round scan, k_reduce (slots past the group's size have zero shares;
+// their rounds are dropped).  The coefficient kernel is 0.15 ms beside a 4.5 ms scan at 2^24 x
+// 1 KiB, and running it on s beside the previous group's scan on aux (two share buffers, as
+// answer_batch_core overlaps its leaf stages) measured no faster on any shape and slower for
+// three groups (16.3 against 14.8 ms for 20 keys: profiles/woodruff_queue/overlap/), so there is
+// one stream and one share buffer.  Five-event layout, fused = 8: "launch" = start -> the first
+// coefficient kernel, "scan" = that -> the end of the last scan, "reduce" = the last group's
+// reduce.  Unshared, and empty ranges: the single answers back to back on s, each with its own
+// slot.
+int answer_woodruff_queue_locked(pir_engine* e, const uint8_t* d_keys, uint32_t M, int nk,
+                                 uint64_t rec0, uint64_t nrec, uint8_t* d_result, hipStream_t s) {
+  const auto& c = e->cfg;
+  const int G = nrec ? woodruff_group(e, nk) : 0;
+  if (int rc = ensure_woodruff_queue(e, M, nk, nrec)) return rc;
+  if (G == 0) {
+    for (int k = 0; k < nk; ++k)
+      if (int rc = answer_woodruff_locked(e, d_keys + (size_t)k * M, M, rec0, nrec,
+                                          d_result + (size_t)k * c.record_bytes, s))
+        return rc;
+    return PIR_OK;
+  }
+  e->ev = nullptr;
+  hipEvent_t* ev = nullptr;
+  if (!e->prof.empty()) {
+    ev = prof_slot(e, 8, 1, true);
+    HIP_TRY(hipEventRecord(ev[EV_START], s));
+  }
+  const pir::ScanShape sh = woodruff_group_shape(e, nrec, G);
+  const int W = sh.nrp;
+  uint8_t* const d_keyT = e->d_cb + wd_share_bytes(nrec, W);
+  if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
+  const int ngroups = (nk + G - 1) / G;
+  for (int q0 = 0, j = 0, ng = 0; q0 < nk; q0 += ng, ++j) {
+    ng = nk / ngroups + (j < nk % ngroups ? 1 : 0);
+    HIP_TRY(pir::launch_woodruff_coefs_g(d_keys + (size_t)q0 * M, M, ng, W, rec0, rec0 + nrec,
+                                         e->d_cb, s, d_keyT));
+    HIP_TRY(pir::launch_scan(sh, e->d_shard + rec0 * e->pitch, nrec, e->d_cb, e->d_slabs, false, s));
+    if (ev && q0 + ng >= nk) HIP_TRY(hipEventRecord(ev[EV_SCAN_E], s));
+    uint8_t* dst = d_result + (size_t)q0 * c.record_bytes;
+    if (ng == sh.nq) {
+      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, dst, s));
+    } else {
+      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, e->d_gtmp, s));
+      HIP_TRY(hipMemcpyAsync(dst, e->d_gtmp, (size_t)ng * c.record_bytes, hipMemcpyDeviceToDevice,
+                             s));
+    }
+  }
+  e->last_fused = 8;
+  if (ev) {
+    HIP_TRY(hipEventRecord(ev[EV_RED], s));
+    HIP_TRY(hipEventRecord(ev[EV_END], s));
+  }
+  return PIR_OK;
+}
+
 // Multiparty sqrt(N) DPF answer (server.cpp:384-430): the thread's rows of the domain
 // [thr * slice * mu, (thr + 1) * slice * mu), slice = nu / num_threads (the reference drops the
 // nu % num_threads remainder rows; so does this), intersected with this engine's partition:
@@ -1366,6 +1487,11 @@ int pir_engine_create(const pir_engine_config* cfg, pir_engine_t** out) {
     if (sg) e->stream_group = std::max(0, std::min(16, atoi(sg)));
     const char* sn = getenv("PIR_STREAM_NARROW");
     e->stream_narrow = sn && atoi(sn) == 1;
+    // $PIR_WD_SHARE / $PIR_WD_G: queued Woodruff keys per shard pass (woodruff_group)
+    const char* ws = getenv("PIR_WD_SHARE");
+    if (ws && ws[0]) e->wd_share = std::max(0, std::min(2, atoi(ws)));
+    const char* wg = getenv("PIR_WD_G");
+    if (wg && wg[0]) e->wd_group = atoi(wg) >= 8 ? 8 : (atoi(wg) >= 4 ? 4 : 2);
     const char* bk = getenv("PIR_BATCH_KLAST");
     if (bk) e->batch_k_last = std::max(1, std::min(12, atoi(bk)));
     const int tile = pir::fused_tile(c.num_rounds, e->pitch, e->rows, e->num_cus);
@@ -2162,6 +2288,62 @@ int pir_engine_answer_woodruff(pir_engine_t* e, const uint8_t* key, uint64_t key
   HIP_TRY(hipStreamSynchronize(e->stream));
   memcpy(result, e->h_res, c.record_bytes);
   return PIR_OK;
+}
+
+int pir_engine_answer_woodruff_queue_dev(pir_engine_t* e, const uint8_t* d_keys, uint64_t key_len,
+                                         int num_keys, uint64_t rec0, uint64_t nrec,
+                                         uint8_t* d_result, void* stream) {
+  if (!e) return fail(PIR_EINVAL, "null argument");
+  if (num_keys < 0) return fail(PIR_EINVAL, "a queue of %d keys", num_keys);
+  if (num_keys > 0 && (!d_keys || !d_result)) return fail(PIR_EINVAL, "null argument");
+  if (int rc = check_woodruff(e, key_len, rec0, nrec)) return rc;
+  if (num_keys == 0) return PIR_OK;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = ws_acquire(e, s)) return rc;
+  return ws_release(e, s, answer_woodruff_queue_locked(e, d_keys, (uint32_t)key_len, num_keys,
+                                                       rec0, nrec, d_result, s));
+}
+
+int pir_engine_answer_woodruff_queue(pir_engine_t* e, const uint8_t* keys, uint64_t key_len,
+                                     int num_keys, uint64_t rec0, uint64_t nrec,
+                                     uint8_t* results) {
+  if (!e) return fail(PIR_EINVAL, "null argument");
+  if (num_keys < 0) return fail(PIR_EINVAL, "a queue of %d keys", num_keys);
+  if (num_keys > 0 && (!keys || !results)) return fail(PIR_EINVAL, "null argument");
+  if (int rc = check_woodruff(e, key_len, rec0, nrec)) return rc;
+  if (num_keys == 0) return PIR_OK;
+  const auto& c = e->cfg;
+  const size_t kb = (size_t)num_keys * key_len, rb = (size_t)num_keys * c.record_bytes;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(c.device));
+  if (int rc = ws_acquire(e, e->stream)) return rc;
+  int rc = ensure_buf(&e->d_coef_stage, &e->coef_stage_cap, kb);
+  if (!rc) rc = ensure_buf(&e->d_shamir_res, &e->shamir_res_cap, rb);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_coef_stage, keys, kb, hipMemcpyHostToDevice, e->stream));
+  rc = ws_release(e, e->stream,
+                  answer_woodruff_queue_locked(e, e->d_coef_stage, (uint32_t)key_len, num_keys,
+                                               rec0, nrec, e->d_shamir_res, e->stream));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(results, e->d_shamir_res, rb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return PIR_OK;
+}
+
+int pir_engine_reserve_woodruff_queue(pir_engine_t* e, int num_keys) {
+  if (!e || num_keys < 1) return fail(PIR_EINVAL, "bad argument");
+  if (int rc = check_woodruff(e, pir::wd_key_len(e->cfg.log_num_records), 0, 0)) return rc;
+  const uint32_t M = pir::wd_key_len(e->cfg.log_num_records);
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  int rc = ensure_woodruff_queue(e, M, num_keys, e->rows);
+  // the host form's staging
+  if (!rc) rc = ensure_buf(&e->d_coef_stage, &e->coef_stage_cap, (size_t)num_keys * M);
+  if (!rc)
+    rc = ensure_buf(&e->d_shamir_res, &e->shamir_res_cap, (size_t)num_keys * e->cfg.record_bytes);
+  return rc;
 }
 
 int pir_engine_answer_woodruff_deriv_dev(pir_engine_t* e, const uint8_t* d_key, uint64_t key_len,

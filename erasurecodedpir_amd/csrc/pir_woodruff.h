@@ -61,6 +61,18 @@ __host__ __device__ inline uint32_t wd_gf_mul(uint32_t a, uint32_t b) {
   return m;
 }
 
+// four such products at once, one per byte lane of a and b (no carry crosses a lane)
+__host__ __device__ inline uint32_t wd_gf_mul4(uint32_t a, uint32_t b) {
+  uint32_t acc = 0;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const uint32_t m = (b >> t) & 0x01010101u;
+    acc ^= a & ((m << 8) - m);  // m * 0xff: the lanes whose bit t of b is set
+    a = ((a & 0x7f7f7f7fu) << 1) ^ (((a >> 7) & 0x01010101u) * 0x1du);
+  }
+  return acc;
+}
+
 // calcWoodruffKeyLength / params.cpp:621-628 for N = 2^n records; 0 when n is outside [0, 31]
 uint32_t wd_key_len(int n);
 
@@ -68,6 +80,19 @@ uint32_t wd_key_len(int n);
 // records [lo, hi): the record-major coefficients of the explicit-coefficient scan
 hipError_t launch_woodruff_coefs(const uint8_t* d_key, uint32_t M, int nrp, uint64_t lo,
                                  uint64_t hi, uint8_t* d_c, hipStream_t s);
+
+// The record-major shares of a group of ng <= W queued keys (d_keys: M bytes each, back to back,
+// any alignment), W in {2, 4, 8} the scan's coefficient bytes per record: byte g of the W at
+// d_c + (i - lo) * W is key_g[a_i] * key_g[b_i] for g < ng and 0 for g >= ng, for the records
+// [lo, hi).  d_c is 16-byte aligned.  One walk of the pairs serves the group: the keys are
+// interleaved into a table keyT[j] = key_0[j] .. key_{W-1}[j] and the W products of a record are
+// one packed multiply (wd_gf_mul4).  The table lives in LDS where its W * M bytes fit
+// (wd_key_table_in_lds), else in d_keyT: W * M bytes of scratch, 8-byte aligned, written by a
+// transposing kernel in front ($PIR_WD_LDS=0 sends every shape that way: tests).
+bool wd_key_table_in_lds(uint32_t M, int W);
+hipError_t launch_woodruff_coefs_g(const uint8_t* d_keys, uint32_t M, int ng, int W, uint64_t lo,
+                                   uint64_t hi, uint8_t* d_c, hipStream_t s,
+                                   uint8_t* d_keyT = nullptr);
 
 // The derivative answers (WOODRUFF_DERIVATIVE = 1, server.cpp:618-644) over the records
 // [lo, hi) of `rows` (pitch bytes apart): M + 1 records of efs bytes at `out`, which the caller

@@ -5,6 +5,8 @@
 // (wd_tile, pir_kernels.hip), which keeps the coefficients in LDS.
 #include "pir_woodruff.h"
 
+#include <stdlib.h>
+
 #include <algorithm>
 
 namespace pir {
@@ -42,6 +44,125 @@ __global__ __launch_bounds__(256) void k_woodruff_coefs(const uint8_t* __restric
       wd_next(M, p);
     }
   }
+}
+
+// ---- queued keys: the shares of a group of keys in one walk (pir_woodruff.h) -----------------
+constexpr uint32_t kWdLdsBytes = 48u << 10;  // the interleaved key table in LDS up to this size
+constexpr unsigned kWdLdsBlocks = 1024;      // ... built once per workgroup, so few workgroups
+
+// keyT[j]: byte g = key_g[j]
+template <int W> struct WdEntry;
+template <> struct WdEntry<2> { using T = uint16_t; };
+template <> struct WdEntry<4> { using T = uint32_t; };
+template <> struct WdEntry<8> { using T = uint2; };
+
+template <int W>
+__device__ __forceinline__ typename WdEntry<W>::T wd_key_entry(const uint8_t* __restrict__ keys,
+                                                               uint32_t M, int ng, uint32_t j) {
+  uint32_t w[2] = {0, 0};
+#pragma unroll
+  for (int g = 0; g < W; ++g)
+    if (g < ng) w[g >> 2] |= (uint32_t)keys[(uint64_t)g * M + j] << (8 * (g & 3));
+  if constexpr (W == 8) return make_uint2(w[0], w[1]);
+  else return (typename WdEntry<W>::T)w[0];
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_woodruff_key_table(const uint8_t* __restrict__ keys,
+                                                            uint32_t M, int ng,
+                                                            typename WdEntry<W>::T* __restrict__ keyT) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j < M) keyT[j] = wd_key_entry<W>(keys, M, ng, j);
+}
+
+// LDS: the workgroup interleaves the keys into LDS first; else keyT is k_woodruff_key_table's
+template <int W, bool LDS>
+__global__ __launch_bounds__(256) void k_woodruff_coefs_g(const uint8_t* __restrict__ keys,
+                                                          const typename WdEntry<W>::T* __restrict__ keyT,
+                                                          uint32_t M, int ng, uint64_t lo,
+                                                          uint64_t hi, uint8_t* __restrict__ dst) {
+  using T = typename WdEntry<W>::T;
+  extern __shared__ uint4 wd_lds[];
+  T* const lt = reinterpret_cast<T*>(wd_lds);
+  if constexpr (LDS) {
+#pragma unroll 4
+    for (uint32_t j = threadIdx.x; j < M; j += 256u) lt[j] = wd_key_entry<W>(keys, M, ng, j);
+    __syncthreads();
+  }
+  auto entry = [&](uint32_t j) __attribute__((always_inline)) -> T {
+    if constexpr (LDS) return lt[j];
+    else return keyT[j];
+  };
+  constexpr int RPS = 16 / W;  // records per 16-byte store
+  const uint64_t nruns = (hi - lo + kWdRun - 1) / kWdRun;
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nruns;
+       r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t i0 = lo + r * kWdRun;
+    const uint64_t i1 = i0 + kWdRun < hi ? i0 + kWdRun : hi;
+    const bool full = i1 - i0 == (uint64_t)kWdRun;
+    WdPair p = wd_pair(M, i0);  // i0 < hi <= the number of pairs: a < b < M, here and below
+    uint32_t pa = p.a;
+    T ka = entry(pa);
+    uint8_t* const d = dst + (i0 - lo) * (uint64_t)W;
+#pragma unroll
+    for (int q = 0; q < kWdRun / RPS; ++q) {
+      uint32_t v[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int u = 0; u < RPS; ++u) {
+        if (i0 + (uint64_t)(q * RPS + u) < i1) {
+          if (p.a != pa) {
+            pa = p.a;
+            ka = entry(pa);
+          }
+          const T kb = entry(p.b);
+          if constexpr (W == 8) {
+            v[2 * u] = wd_gf_mul4(ka.x, kb.x);
+            v[2 * u + 1] = wd_gf_mul4(ka.y, kb.y);
+          } else if constexpr (W == 4) {
+            v[u] = wd_gf_mul4(ka, kb);
+          } else {
+            v[u >> 1] |= wd_gf_mul4(ka, kb) << (16 * (u & 1));
+          }
+          wd_next(M, p);
+        }
+      }
+      if (full) {
+        *reinterpret_cast<uint4*>(d + q * 16) = make_uint4(v[0], v[1], v[2], v[3]);
+      } else {  // the range's last run: record by record
+#pragma unroll
+        for (int u = 0; u < RPS; ++u) {
+          if (i0 + (uint64_t)(q * RPS + u) >= i1) continue;
+          uint8_t* const o = d + (q * RPS + u) * W;
+          if constexpr (W == 8) *reinterpret_cast<uint2*>(o) = make_uint2(v[2 * u], v[2 * u + 1]);
+          else if constexpr (W == 4) *reinterpret_cast<uint32_t*>(o) = v[u];
+          else *reinterpret_cast<uint16_t*>(o) = (uint16_t)(v[u >> 1] >> (16 * (u & 1)));
+        }
+      }
+    }
+  }
+}
+
+template <int W>
+hipError_t coefs_g(const uint8_t* d_keys, uint32_t M, int ng, uint64_t lo, uint64_t hi,
+                   uint8_t* d_c, hipStream_t s, uint8_t* d_keyT, bool lds) {
+  using T = typename WdEntry<W>::T;
+  const uint64_t nruns = (hi - lo + kWdRun - 1) / kWdRun;
+  const uint64_t blocks = (nruns + 255) / 256;
+  if (lds) {
+    const size_t bytes = ((size_t)M * W + 15) & ~(size_t)15;
+    hipLaunchKernelGGL((k_woodruff_coefs_g<W, true>),
+                       dim3((unsigned)std::min<uint64_t>(blocks, kWdLdsBlocks)), dim3(256), bytes, s,
+                       d_keys, (const T*)nullptr, M, ng, lo, hi, d_c);
+    return hipGetLastError();
+  }
+  if (!d_keyT || reinterpret_cast<uintptr_t>(d_keyT) % 8 != 0) return hipErrorInvalidValue;
+  T* const keyT = reinterpret_cast<T*>(d_keyT);
+  hipLaunchKernelGGL((k_woodruff_key_table<W>), dim3((M + 255u) / 256u), dim3(256), 0, s, d_keys,
+                     M, ng, keyT);
+  hipLaunchKernelGGL((k_woodruff_coefs_g<W, false>),
+                     dim3((unsigned)std::min<uint64_t>(blocks, 1u << 16)), dim3(256), 0, s, d_keys,
+                     (const T*)keyT, M, ng, lo, hi, d_c);
+  return hipGetLastError();
 }
 
 // ---- derivative answers (server.cpp:618-644) -------------------------------------------------
@@ -281,6 +402,26 @@ hipError_t launch_woodruff_coefs(const uint8_t* d_key, uint32_t M, int nrp, uint
   const dim3 grid((unsigned)std::min<uint64_t>((nruns + 255) / 256, 1u << 16));
   hipLaunchKernelGGL(k_woodruff_coefs, grid, dim3(256), 0, s, d_key, M, nrp, lo, hi, d_c);
   return hipGetLastError();
+}
+
+bool wd_key_table_in_lds(uint32_t M, int W) {
+  const char* v = getenv("PIR_WD_LDS");
+  return (uint64_t)M * W <= kWdLdsBytes && !(v && atoi(v) == 0);
+}
+
+hipError_t launch_woodruff_coefs_g(const uint8_t* d_keys, uint32_t M, int ng, int W, uint64_t lo,
+                                   uint64_t hi, uint8_t* d_c, hipStream_t s, uint8_t* d_keyT) {
+  if (lo >= hi) return hipSuccess;
+  if (M < 3 || M >= (1u << 17) || hi > (uint64_t)M * (M - 1) / 2 || ng < 1 || ng > W ||
+      reinterpret_cast<uintptr_t>(d_c) % 16 != 0)
+    return hipErrorInvalidValue;
+  const bool lds = wd_key_table_in_lds(M, W);
+  switch (W) {
+    case 2: return coefs_g<2>(d_keys, M, ng, lo, hi, d_c, s, d_keyT, lds);
+    case 4: return coefs_g<4>(d_keys, M, ng, lo, hi, d_c, s, d_keyT, lds);
+    case 8: return coefs_g<8>(d_keys, M, ng, lo, hi, d_c, s, d_keyT, lds);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace pir

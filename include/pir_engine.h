@@ -22,6 +22,8 @@
  *   pir_engine_shamir_response_len   calcShamirResponseLength               utils.cpp:140-143
  *   pir_engine_answer_woodruff[_dev] runWoodruffQueryThread (value answer)  server.cpp:564-616
  *   pir_engine_answer_woodruff_deriv[_dev]  ... with WOODRUFF_DERIVATIVE    server.cpp:618-644
+ *   pir_engine_answer_woodruff_queue[_dev]  K value answers, 8 keys per read of the shard
+ *   pir_engine_reserve_woodruff_queue       (no counterpart: the reference answers one key)
  *   pir_engine_woodruff_m            calcWoodruffKeyLength / WOODRUFF_M     params.cpp:621-628
  *   pir_engine_woodruff_pair         makeCombi(M, 2)[i] - 1                 params.cpp:629-640
  *   pir_engine_answer_mp[_dev]       runOptimizedMultiPartyDPFQuery[Thread] server.cpp:136-176,
@@ -216,6 +218,27 @@ int pir_engine_answer_woodruff_deriv(pir_engine_t *e, const uint8_t *key, uint64
 int pir_engine_answer_woodruff_deriv_dev(pir_engine_t *e, const uint8_t *d_key, uint64_t key_len,
                                          uint64_t rec0, uint64_t nrec, uint8_t *d_result,
                                          void *stream);
+/* A queue of num_keys independent Woodruff value queries over the records [rec0, rec0 + nrec):
+ * keys of key_len = M bytes back to back, results num_keys x record_bytes back to back, result k
+ * byte for byte what pir_engine_answer_woodruff[_dev] gives for key k and the same range.  The
+ * refusals are those of the single answer; num_keys < 0 and, with num_keys > 0, null pointers are
+ * PIR_EINVAL; num_keys == 0 writes nothing, nrec == 0 zeroes every result.  A shared queue goes
+ * into ceil(K / G) groups of as equal sizes as possible (20 -> 7 + 7 + 6); one coefficient kernel
+ * writes a group's pair products for every record (the keys interleaved, the group's products
+ * one packed GF(2^8) multiply) and one G-round scan reads the shard once for the group.
+ * $PIR_WD_SHARE, read at engine creation: 0 never shares (the single answers back to back on the
+ * stream), unset or 1 follows the measured policy (Queued Woodruff queries share
+ * shard passes), 2 shares every queue of two or more keys; $PIR_WD_G overrides the keys per pass
+ * (2, 4 or 8; default 8).  The device form is asynchronous on `stream`; the keys may have any
+ * alignment. */
+int pir_engine_answer_woodruff_queue_dev(pir_engine_t *e, const uint8_t *d_keys, uint64_t key_len,
+                                         int num_keys, uint64_t rec0, uint64_t nrec,
+                                         uint8_t *d_result, void *stream);
+int pir_engine_answer_woodruff_queue(pir_engine_t *e, const uint8_t *keys, uint64_t key_len,
+                                     int num_keys, uint64_t rec0, uint64_t nrec, uint8_t *results);
+/* pre-size everything the queue touches for up to num_keys keys, so that a later queue call
+ * allocates nothing (as pir_engine_reserve_queue does for tree queues) */
+int pir_engine_reserve_woodruff_queue(pir_engine_t *e, int num_keys);
 /* the tile (records) of the single-launch path that answers this engine's whole domain when
  * $PIR_WD_FUSED selects it (k_query's Woodruff mode), 0 where its shape is not served and every
  * answer goes through the coefficient kernel + scan */
@@ -314,7 +337,10 @@ int pir_engine_memcpy_d2h(pir_engine_t *e, void *h_dst, const void *d_src, size_
  * the Hermite scan, reduce = the Hermite slabs' k_reduce + the totals kernel.  A Woodruff answer
  * (fused = 5: the single launch, 6: coefficient kernel + scan) reports them too: launch = start
  * -> the first kernel, scan = that kernel (6: both kernels), reduce = k_reduce; its derivative
- * answers (fused = 7): launch = start -> the answer zeroed, scan = the two passes, reduce = 0. */
+ * answers (fused = 7): launch = start -> the answer zeroed, scan = the two passes, reduce = 0.
+ * A shared Woodruff queue (fused = 8) has one event set: launch = start -> the first coefficient
+ * kernel, scan = that -> the end of the last group's scan, reduce = the last group's k_reduce;
+ * an unshared queue records what its single answers record. */
 typedef struct {
     char name[32];
     float ms;

@@ -19,8 +19,24 @@ the spread the run shows between repeats of one leg.
 
     python tools/bench_woodruff.py [--log-records 24] [--record-bytes 1024] [--iters 10]
                                    [--warmup 3] [--no-deriv]
+
+--queue measures queues of Woodruff value queries instead (pir_engine_answer_woodruff_queue_dev;
+the knobs are read at engine creation, so every leg has its own engine over the same shard
+bytes), for each queue length of --queue-lengths (default 2,4,8,20):
+
+  shared     $PIR_WD_SHARE=2: G keys per read of the shard (coefficient kernel, G-round scan)
+  unshared   $PIR_WD_SHARE=0: the single answers back to back
+  parent     --parent-lib PATH, the parent commit's library built into a second directory: K
+             back-to-back pir_engine_answer_woodruff_dev calls on one stream
+
+and prints ONE JSON line: per queue length and leg the median, min and max ms and ms per key,
+the largest max - min spread of any leg, shared against parent, and `shared_equals_unshared`,
+a byte comparison of the two legs' answers at full size.
+
+    python tools/bench_woodruff.py --queue [--parent-lib DIR/libpir_engine.so] [--queue-lengths 2,4,8,20]
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -35,6 +51,91 @@ import erasurecodedpir_amd as pir  # noqa: E402
 from bench_shamir import Events, hip_runtime  # noqa: E402
 
 
+def other_library_engine(path, *args):
+    """An Engine that runs on another build of the library (one without the queue calls too)."""
+    from erasurecodedpir_amd import _lib
+    other = ctypes.CDLL(path)
+    for name, (res, argtypes) in _lib.PROTOTYPES.items():
+        fn = getattr(other, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, argtypes
+    mine = _lib.load()
+    _lib._lib = other
+    try:
+        return pir.Engine(*args)
+    finally:
+        _lib._lib = mine
+
+
+def queue_bench(a):
+    n, efs = a.log_records, a.record_bytes
+    N, M = 1 << n, pir.woodruff_m(n)
+    lengths = [int(x) for x in a.queue_lengths.split(",")]
+    kmax = max(lengths)
+    ev = Events(hip_runtime())
+    keys = np.random.default_rng(5).integers(0, 256, (kmax, M), dtype=np.uint8)
+    engines, bufs = {}, {}
+    for leg, env in (("shared", {"PIR_WD_SHARE": "2"}), ("unshared", {"PIR_WD_SHARE": "0"})):
+        os.environ.update(env)
+        engines[leg] = pir.Engine(2, 1, n, efs, 1)
+        for k in env:
+            del os.environ[k]
+    if a.parent_lib:
+        engines["parent"] = other_library_engine(a.parent_lib, 2, 1, n, efs, 1)
+    for leg, e in engines.items():
+        e.fill_shard_random(15)
+        bufs[leg] = (e.alloc_dev(kmax * M), e.alloc_dev(kmax * efs))
+        e.h2d(bufs[leg][0], keys.reshape(-1))
+        if leg != "parent":
+            e.reserve_woodruff_queue(kmax)
+
+    def run(leg, K):
+        e, (d_k, d_r) = engines[leg], bufs[leg]
+        if leg == "parent":
+            for k in range(K):
+                e.answer_woodruff_dev(d_k + k * M, M, 0, N, d_r + k * efs)
+        else:
+            e.answer_woodruff_queue_dev(d_k, M, K, 0, N, d_r)
+
+    out = {"bench": "woodruff_queue", "log_records": n, "record_bytes": efs, "key_len": M,
+           "iters": a.iters, "warmup": a.warmup, "shard_bytes": N * efs,
+           "parent_lib": bool(a.parent_lib), "queues": {}}
+    same, spread = True, 0.0
+    for K in lengths:
+        got = {}
+        for leg in engines:
+            run(leg, K)
+            engines[leg].sync()
+            got[leg] = engines[leg].d2h(bufs[leg][1], K * efs).copy()
+        same = same and all(np.array_equal(got["shared"], g) for g in got.values())
+        for _ in range(a.warmup):
+            for leg in engines:
+                run(leg, K)
+        for e in engines.values():
+            e.sync()
+        ms = {leg: [] for leg in engines}
+        for _ in range(a.iters):
+            for leg, e in engines.items():
+                ms[leg].append(ev.time(e.stream, lambda: run(leg, K)))
+        q = {}
+        for leg, v in ms.items():
+            med = statistics.median(v)
+            q[leg] = {"ms": round(med, 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                      "spread": round(max(v) - min(v), 4), "ms_per_key": round(med / K, 4)}
+            spread = max(spread, max(v) - min(v))
+        out["queues"][str(K)] = q
+    out["shared_equals_unshared"] = bool(same)
+    out["largest_spread_ms"] = round(spread, 4)
+    if a.parent_lib:
+        for K in lengths:
+            q = out["queues"][str(K)]
+            q["parent_minus_shared_ms"] = round(q["parent"]["ms"] - q["shared"]["ms"], 4)
+            q["shared_beats_parent"] = bool(q["parent"]["ms"] - q["shared"]["ms"] > spread)
+    for e in engines.values():
+        e.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-records", type=int, default=24)
@@ -42,7 +143,12 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-deriv", action="store_true")
+    ap.add_argument("--queue", action="store_true")
+    ap.add_argument("--queue-lengths", default="2,4,8,20")
+    ap.add_argument("--parent-lib", default="")
     a = ap.parse_args()
+    if a.queue:
+        return queue_bench(a)
     n, efs = a.log_records, a.record_bytes
     N, M = 1 << n, pir.woodruff_m(n)
     ev = Events(hip_runtime())
