@@ -122,6 +122,13 @@ PROTOTYPES = {
     "pir_engine_answer_cd_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "pir_engine_cd_key_len": (_I, [_I, _I, _I, _I, _I]),
     "pir_engine_mp_eval_bytes": (ctypes.c_longlong, [_I, _I, _I]),
+    "pir_engine_answer_coefs_queue_dev": (_I, [_P, _P, _U64, _U64, _I, _U64, _U64, _P, _P]),
+    "pir_engine_answer_coefs_queue": (_I, [_P, ctypes.POINTER(_P), _I, _U64, _U64, _P]),
+    "pir_engine_answer_mp_queue_dev": (_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _P, _P]),
+    "pir_engine_answer_mp_queue": (_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _P]),
+    "pir_engine_answer_cd_queue_dev": (_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _P, _P]),
+    "pir_engine_answer_cd_queue": (_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _P]),
+    "pir_engine_reserve_group_queue": (_I, [_P, _I]),
     "pir_engine_answer_dev": (_I, [_P, _P, _P, _P]),
     "pir_engine_answer_batch_dev": (_I, [_P, _P, _I, _P, _P]),
     "pir_engine_answer_batch": (_I, [_P, _P, _I, _P]),

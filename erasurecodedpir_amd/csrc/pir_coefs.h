@@ -12,6 +12,14 @@ namespace pir {
 hipError_t launch_interleave_coefs(const uint8_t* src, uint64_t src_pitch, uint64_t nrows, int nq,
                                    int nrp, uint8_t* d_c, hipStream_t s);
 
+// The vectors of a group of ng queued keys as one W-byte share row per record (W = 2, 4 or 8; W
+// >= ng * nrp): d_c[i * W + g * nrp + a] = src[g * key_stride + a * coef_pitch + i] for g < ng and
+// a < nq, zero for every other byte, i < nrows.  d_c 16-byte aligned; the vectors may have any
+// alignment (an aligned one is read with 16-byte loads).
+hipError_t launch_interleave_coefs_g(const uint8_t* src, uint64_t coef_pitch, uint64_t key_stride,
+                                     int ng, int nq, int nrp, int W, uint64_t nrows, uint8_t* d_c,
+                                     hipStream_t s);
+
 // The Hollanti-mode shard, encoded within files on the GPU (client.cpp:43-56, 99-103; the
 // shim's encode_within_files_server): row r (file r, r < num_files; rows past are zero) =
 // XOR_{j<k} gf_pow(party, j) * part j of file r, part j = bytes [j*efs, (j+1)*efs) of the

@@ -4,6 +4,7 @@
 // lane writes its record's nrp bytes (one 1/2/4/8/16-byte store).  HBM-bound: nq + nrp bytes
 // per record, against the record_bytes of shard the scan then reads.
 #include "pir_coefs.h"
+#include "pir_transpose.h"
 
 #include <algorithm>
 
@@ -48,6 +49,79 @@ hipError_t launch_interleave_coefs(const uint8_t* src, uint64_t src_pitch, uint6
     default: return hipErrorInvalidValue;
   }
 #undef PIR_IL
+  return hipGetLastError();
+}
+
+// ---- k_interleave_coefs_g: the vectors of a group of queued keys -> one W-byte share row ----
+// Byte b of a record's share row is round a = b % nrp of key slot g = b / nrp (zero for g >= ng
+// and a >= nq).  One thread = 16 consecutive records: a 16-byte load per vector whose address
+// is aligned (byte loads at the range's tail and for vectors that are not), the byte transpose
+// of pir_transpose.h in registers, W 16-byte stores.  HBM-bound: (ng nq + W) bytes per record.
+template <int W>
+__global__ __launch_bounds__(256) void k_interleave_coefs_g(
+    const uint8_t* __restrict__ src, uint64_t coef_pitch, uint64_t key_stride, int ng, int nq,
+    int lg_nrp, uint64_t nrows, uint8_t* __restrict__ dst) {
+  const uint64_t nitems = (nrows + 15) / 16;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nitems;
+       t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t i0 = 16 * t;
+    const int cnt = (int)(nrows - i0 < 16 ? nrows - i0 : 16);
+    uint4 v[W];
+#pragma unroll
+    for (int b = 0; b < W; ++b) {
+      const int g = b >> lg_nrp, a = b & ((1 << lg_nrp) - 1);
+      v[b] = make_uint4(0, 0, 0, 0);
+      if (g < ng && a < nq) {
+        const uint8_t* p = src + (uint64_t)g * key_stride + (uint64_t)a * coef_pitch + i0;
+        if (cnt == 16 && ((uintptr_t)p & 15) == 0) {
+          v[b] = *reinterpret_cast<const uint4*>(p);
+        } else {
+          uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+#pragma unroll
+          for (int k = 0; k < 16; ++k) {
+            const uint32_t x = k < cnt ? (uint32_t)p[k] << (8 * (k & 3)) : 0u;
+            if (k < 4) w0 |= x; else if (k < 8) w1 |= x; else if (k < 12) w2 |= x; else w3 |= x;
+          }
+          v[b] = make_uint4(w0, w1, w2, w3);
+        }
+      }
+    }
+    if (cnt == 16) {
+      uint4 o[W];
+      tr_records<W>(v, o);
+      uint4* out = reinterpret_cast<uint4*>(dst + i0 * W);
+#pragma unroll
+      for (int m = 0; m < W; ++m) out[m] = o[m];
+    } else {  // the range's tail: byte stores
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < cnt) {
+#pragma unroll
+          for (int b = 0; b < W; ++b) dst[(i0 + k) * W + b] = (uint8_t)tr_byte(v[b], k);
+        }
+    }
+  }
+}
+
+hipError_t launch_interleave_coefs_g(const uint8_t* src, uint64_t coef_pitch, uint64_t key_stride,
+                                     int ng, int nq, int nrp, int W, uint64_t nrows, uint8_t* d_c,
+                                     hipStream_t s) {
+  if (nrows == 0) return hipSuccess;
+  int lg = 0;
+  while ((1 << lg) < nrp) ++lg;
+  if ((1 << lg) != nrp || nq < 1 || nq > nrp || ng < 1 || ng * nrp > W ||
+      ((uintptr_t)d_c & 15) != 0)
+    return hipErrorInvalidValue;
+  const uint64_t nitems = (nrows + 15) / 16;
+  const dim3 grid((unsigned)std::min<uint64_t>((nitems + 255) / 256, 1u << 16));
+#define PIR_ILG(N) hipLaunchKernelGGL(k_interleave_coefs_g<N>, grid, dim3(256), 0, s, src, coef_pitch, key_stride, ng, nq, lg, nrows, d_c)
+  switch (W) {
+    case 2: PIR_ILG(2); break;
+    case 4: PIR_ILG(4); break;
+    case 8: PIR_ILG(8); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef PIR_ILG
   return hipGetLastError();
 }
 

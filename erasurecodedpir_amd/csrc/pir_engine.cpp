@@ -144,6 +144,9 @@ struct pir_engine {
   bool stream_narrow = false;   // $PIR_STREAM_NARROW=1: narrower scans for short groups (diagnostics)
   int wd_share = 1;             // $PIR_WD_SHARE: 0 never, 1 woodruff_share_policy, 2 every queue of >= 2
   int wd_group = 0;             // $PIR_WD_G: keys per pass of a shared Woodruff queue (0: 8)
+  int gq_share = 1;             // $PIR_GQ_SHARE: 0 never, 1 group_share_policy, 2 every queue of >= 2
+  int gq_group = 0;             // $PIR_GQ_G: key slots per pass of a shared group queue (0: 8 / nrp)
+  uint64_t gq_key_bytes = 0;    // the longest sqrt(N) key a queue has staged (reserve_group_queue)
   int batch_scan_bpc = 2;       // scan workgroups per CU in batched answers ($PIR_BATCH_SCAN_BPC)
   int batch_k_last = -1;        // levels of the batched leaf stage (-1: make_plan's; $PIR_BATCH_KLAST)
   uint8_t* d_result = nullptr;  // nq*efs (host-API staging)
@@ -712,7 +715,8 @@ constexpr int kNumPhases = 9;
 // "launch" = answer start -> its first kernel, "scan" = that kernel (with 6, both), "reduce" =
 // k_reduce; its derivative answers (fused == 7): "launch" = start -> the answer zeroed, "scan" =
 // the rows pass, the totals kernel and the columns pass, "reduce" = 0; a shared Woodruff queue
-// (fused == 8): answer_woodruff_queue_locked
+// (fused == 8) and a shared queue of explicit-coefficient or sqrt(N) DPF keys (fused == 9):
+// answer_group_queue
 const char* const kQueryPhaseNames[] = {"launch", "scan", "reduce", "comm_fold", "total", "fused"};
 constexpr int kNumQueryPhases = 6;
 
@@ -1179,7 +1183,8 @@ int woodruff_group(const pir_engine* e, int nk) {
 }
 
 // a group of G key slots over nrec records: record-major shares (the coefficient kernel writes
-// all of a record's bytes at once), whichever scan takes them
+// all of a record's bytes at once), whichever scan takes them.  Every group queue's shape
+// (answer_group_queue), G * nrp rounds wide
 pir::ScanShape woodruff_group_shape(const pir_engine* e, uint64_t nrec, int G) {
   bool kmaj = false;
   pir::ScanShape sh = group_scan_shape(e, nrec, G, G, &kmaj);
@@ -1189,6 +1194,58 @@ pir::ScanShape woodruff_group_shape(const pir_engine* e, uint64_t nrec, int G) {
 }
 
 size_t wd_share_bytes(uint64_t nrec, int W) { return ((size_t)nrec * W + 15) & ~(size_t)15; }
+
+// The group loop of every queue whose keys become record-major share rows (the Woodruff queue,
+// the explicit-coefficient queue, the sqrt(N) DPF queues): nk keys over the engine rows [row0,
+// row0 + nrec), G key slots of nrp bytes per pass (W = G nrp <= 8).  The keys go into ceil(nk / G)
+// groups of as equal sizes as possible (20 at G = 8: 7 + 7 + 6), as answer_batch_core's queue
+// does; per group, on s alone and with the one share buffer d_cb: write(q0, ng, d_cb, s) writes
+// the W-byte share rows of the keys [q0, q0 + ng) (key slot g at bytes [g nrp, (g + 1) nrp) of
+// each record; slots past ng and rounds past num_rounds zero), the full-width scan reads the
+// shard once, and k_reduce writes straight into the results for a full group with nrp ==
+// num_rounds, else into d_gtmp, from where the group's slots and rounds are copied (the empty
+// slots' and padded rounds' outputs are dropped, as in answer_batch_core).  d_result: nk x
+// num_rounds x record_bytes.  The caller has sized d_cb, the slabs and d_gtmp.  Five-event
+// layout with fused = path: "launch" = start -> the first share kernel, "scan" = that -> the end
+// of the last scan, "reduce" = the last group's reduce.
+template <class Writer>
+int answer_group_queue(pir_engine* e, int nk, int G, int path, uint64_t row0, uint64_t nrec,
+                       uint8_t* d_result, hipStream_t s, Writer&& write) {
+  const auto& c = e->cfg;
+  const size_t out_bytes = (size_t)c.num_rounds * c.record_bytes;
+  e->ev = nullptr;
+  hipEvent_t* ev = nullptr;
+  if (!e->prof.empty()) {
+    ev = prof_slot(e, path, 1, true);
+    HIP_TRY(hipEventRecord(ev[EV_START], s));
+  }
+  const pir::ScanShape sh = woodruff_group_shape(e, nrec, G);
+  if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
+  const int ngroups = (nk + G - 1) / G;
+  for (int q0 = 0, j = 0, ng = 0; q0 < nk; q0 += ng, ++j) {
+    ng = nk / ngroups + (j < nk % ngroups ? 1 : 0);
+    HIP_TRY(write(q0, ng, e->d_cb, s));
+    HIP_TRY(pir::launch_scan(sh, e->d_shard + row0 * e->pitch, nrec, e->d_cb, e->d_slabs, false, s));
+    if (ev && q0 + ng >= nk) HIP_TRY(hipEventRecord(ev[EV_SCAN_E], s));
+    uint8_t* dst = d_result + (size_t)q0 * out_bytes;
+    if (e->nrp == c.num_rounds && ng * e->nrp == sh.nq) {
+      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, dst, s));
+    } else {
+      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, e->d_gtmp, s));
+      if (e->nrp == c.num_rounds)
+        HIP_TRY(hipMemcpyAsync(dst, e->d_gtmp, (size_t)ng * out_bytes, hipMemcpyDeviceToDevice, s));
+      else
+        HIP_TRY(hipMemcpy2DAsync(dst, out_bytes, e->d_gtmp, (size_t)e->nrp * c.record_bytes,
+                                 out_bytes, ng, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  e->last_fused = path;
+  if (ev) {
+    HIP_TRY(hipEventRecord(ev[EV_RED], s));
+    HIP_TRY(hipEventRecord(ev[EV_END], s));
+  }
+  return PIR_OK;
+}
 
 // every buffer a Woodruff queue of up to nk keys over up to nrec records touches, shared or not
 int ensure_woodruff_queue(pir_engine* e, uint32_t M, int nk, uint64_t nrec) {
@@ -1234,38 +1291,14 @@ int answer_woodruff_queue_locked(pir_engine* e, const uint8_t* d_keys, uint32_t 
         return rc;
     return PIR_OK;
   }
-  e->ev = nullptr;
-  hipEvent_t* ev = nullptr;
-  if (!e->prof.empty()) {
-    ev = prof_slot(e, 8, 1, true);
-    HIP_TRY(hipEventRecord(ev[EV_START], s));
-  }
-  const pir::ScanShape sh = woodruff_group_shape(e, nrec, G);
-  const int W = sh.nrp;
+  const int W = G * e->nrp;
   uint8_t* const d_keyT = e->d_cb + wd_share_bytes(nrec, W);
-  if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
-  const int ngroups = (nk + G - 1) / G;
-  for (int q0 = 0, j = 0, ng = 0; q0 < nk; q0 += ng, ++j) {
-    ng = nk / ngroups + (j < nk % ngroups ? 1 : 0);
-    HIP_TRY(pir::launch_woodruff_coefs_g(d_keys + (size_t)q0 * M, M, ng, W, rec0, rec0 + nrec,
-                                         e->d_cb, s, d_keyT));
-    HIP_TRY(pir::launch_scan(sh, e->d_shard + rec0 * e->pitch, nrec, e->d_cb, e->d_slabs, false, s));
-    if (ev && q0 + ng >= nk) HIP_TRY(hipEventRecord(ev[EV_SCAN_E], s));
-    uint8_t* dst = d_result + (size_t)q0 * c.record_bytes;
-    if (ng == sh.nq) {
-      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, dst, s));
-    } else {
-      HIP_TRY(pir::launch_reduce(sh, e->d_slabs, c.record_bytes, e->d_gtmp, s));
-      HIP_TRY(hipMemcpyAsync(dst, e->d_gtmp, (size_t)ng * c.record_bytes, hipMemcpyDeviceToDevice,
-                             s));
-    }
-  }
-  e->last_fused = 8;
-  if (ev) {
-    HIP_TRY(hipEventRecord(ev[EV_RED], s));
-    HIP_TRY(hipEventRecord(ev[EV_END], s));
-  }
-  return PIR_OK;
+  return answer_group_queue(e, nk, G, 8, rec0, nrec, d_result, s,
+                            [&](int q0, int ng, uint8_t* d_cb, hipStream_t st) {
+                              return pir::launch_woodruff_coefs_g(d_keys + (size_t)q0 * M, M, ng, W,
+                                                                  rec0, rec0 + nrec, d_cb, st,
+                                                                  d_keyT);
+                            });
 }
 
 // Multiparty sqrt(N) DPF answer (server.cpp:384-430): the thread's rows of the domain
@@ -1360,6 +1393,176 @@ int check_cd(const pir_engine* e, int q_needed, int num_cd_keys, int thread_num,
     return fail(PIR_EINVAL, "no covering-design DPF layout for NUM_CD_KEYS_NEEDED=%d "
                 "NUM_CD_KEYS=%d n=%d", q_needed, num_cd_keys, e->cfg.log_num_records);
   return check_layout(e, *L, thread_num, num_threads, "covering-design (NUM_CD_KEYS)");
+}
+
+// ---- queues of explicit-coefficient and sqrt(N) DPF keys (fused == 9) --------------------------
+// Key slots per shard pass of a queue of nk keys by default; 0: every key its own answer, back to
+// back.  mode 0: explicit-coefficient vectors, 1: multiparty / covering-design keys.  A pure
+// function of the shape, on only for the families where the shared queue measured faster than the
+// parent build's back-to-back single answers by more than the largest spread of any leg of that
+// run (tools/bench_group_queue.py, profiles/group_queue/README.md); a family nobody measured
+// stays off.
+// seeds: the sqrt(N) layout's seeds per row (0 for mode 0).
+int group_share_policy(int mode, int num_rounds, uint32_t seeds, uint32_t pitch, uint64_t rows,
+                       int nk) {
+  // measured: queues of 2, 4, 8 and 20 keys over 2^20 and 2^24 rows of 1 KiB and 2^24 of 256 B;
+  // vectors of 1 and 2 rounds, multiparty p = 3 / t = 1 (2 shares, 4 seeds), CD842 (3 shares, 32
+  // seeds).  Vectors and multiparty, 4 keys and more: 2.1-2.7x the parent at 4, 4.5-4.7x (1
+  // round) and 2.1-2.7x (2 rounds / shares: 4 slots) at 8 and 20, on every shape; 2 keys: 1.07-
+  // 1.36x, inside the spread on one or two of the three shapes, so they stay unshared.  CD842 (2
+  // slots): 1.67-1.70x at 256 B for every length (its single answer there is bound by the AES of
+  // its 32 seeds, which a group does once per key all the same, but beside one scan); 0.97-1.00x
+  // at 2^24 x 1 KiB and 0.69x at 2^20 x 1 KiB, where the single answer's k_query hides the share
+  // waves under its scan and the group's share kernel (1.28 ms for two keys) does not: off
+  const bool kib = pitch == 1024 && rows >= (1ull << 20);
+  const bool b256 = pitch == 256 && rows >= (1ull << 24);
+  if (mode == 0) return num_rounds <= 2 && nk >= 4 && (kib || b256) ? 8 / num_rounds : 0;
+  if (num_rounds == 2 && seeds == 4) return nk >= 4 && (kib || b256) ? 4 : 0;
+  if (num_rounds == 3 && seeds == 32) return nk >= 2 && b256 ? 2 : 0;
+  return 0;
+}
+
+// the key slots per pass of a group queue of nk keys (0: unshared).  $PIR_GQ_SHARE: 0 never
+// shares, 1 (default) follows group_share_policy, 2 shares every queue of two or more keys that
+// has two or more slots (nrp <= 4; 8 / nrp slots); $PIR_GQ_G overrides the slots per pass.  A
+// communicator's queue runs the single answers, each with its own exchange.
+int group_queue_slots(const pir_engine* e, int mode, int nk, uint32_t seeds = 0) {
+  const auto& c = e->cfg;
+  if (e->gq_share == 0 || nk < 2 || e->nrp > 4 || e->comm) return 0;
+  int g = group_share_policy(mode, c.num_rounds, seeds, e->pitch, e->rows, nk);
+  if (g == 0 && e->gq_share < 2) return 0;
+  const int gmax = 8 / e->nrp;
+  if (g == 0 || g > gmax) g = gmax;
+  if (e->gq_group > 0) g = std::min(e->gq_group, gmax);
+  return g >= 2 ? g : 0;
+}
+
+// the buffers a shared group queue over nrec rows touches, G slots per pass
+int ensure_group_queue(pir_engine* e, uint64_t nrec, int G) {
+  const pir::ScanShape sh = woodruff_group_shape(e, nrec, G);
+  int rc = ensure_slabs(e, (size_t)sh.grid.x * sh.grid.y * sh.slab_bytes);
+  if (!rc) rc = ensure_buf(&e->d_cb, &e->cb_cap, wd_share_bytes(nrec, G * e->nrp));
+  if (!rc && !e->d_gtmp) HIP_TRY(hipMalloc(&e->d_gtmp, (size_t)16 * e->cfg.record_bytes));
+  return rc;
+}
+
+// A queue of nk explicit-coefficient queries over the engine rows [row0, row0 + nrows): key k's
+// round a coefficient of row row0 + i at src[k * key_stride + a * coef_pitch + i]; d_result nk x
+// num_rounds x efs, result k what answer_coefs_locked gives for key k.  G > 0 (group_queue_slots):
+// k_interleave_coefs_g writes each group's share rows (answer_group_queue); G == 0, and empty
+// ranges: the single answers back to back on s.
+int answer_coefs_queue_locked(pir_engine* e, const uint8_t* src, uint64_t coef_pitch,
+                              uint64_t key_stride, int nk, int G, uint64_t row0, uint64_t nrows,
+                              uint8_t* d_result, hipStream_t s) {
+  const auto& c = e->cfg;
+  const size_t out_bytes = (size_t)c.num_rounds * c.record_bytes;
+  if (G == 0 || nrows == 0) {
+    for (int k = 0; k < nk; ++k)
+      if (int rc = answer_coefs_locked(e, src + (size_t)k * key_stride, coef_pitch, row0, nrows,
+                                       d_result + (size_t)k * out_bytes, s))
+        return rc;
+    return PIR_OK;
+  }
+  if (int rc = ensure_group_queue(e, nrows, G)) return rc;
+  const int W = G * e->nrp;
+  return answer_group_queue(e, nk, G, 9, row0, nrows, d_result, s,
+                            [&](int q0, int ng, uint8_t* d_cb, hipStream_t st) {
+                              return pir::launch_interleave_coefs_g(
+                                  src + (size_t)q0 * key_stride, coef_pitch, key_stride, ng,
+                                  c.num_rounds, e->nrp, W, nrows, d_cb, st);
+                            });
+}
+
+// A queue of nk sqrt(N) DPF keys of one layout (multiparty or covering-design), 16-byte aligned
+// and key_stride (a multiple of 16) apart, over the thread slice of answer_mp_locked; result k
+// what answer_mp_locked gives for key k.  Shared: k_mp_shares_g writes each group's share rows.
+// Unshared, an empty slice and nu == 0: the single answers back to back on s.
+int answer_mp_queue_locked(pir_engine* e, const pir::MpLayout& L, const uint8_t* d_keys,
+                           uint64_t key_stride, int nk, int thread_num, int num_threads,
+                           uint8_t* d_result, hipStream_t s) {
+  const auto& c = e->cfg;
+  const size_t out_bytes = (size_t)c.num_rounds * c.record_bytes;
+  const uint64_t slice = L.nu / (uint64_t)num_threads;
+  const uint64_t p0 = (uint64_t)c.partition_index * e->rows;
+  const uint64_t lo = std::max<uint64_t>((uint64_t)thread_num * slice * L.mu, p0);
+  const uint64_t hi = std::min<uint64_t>((uint64_t)(thread_num + 1) * slice * L.mu, p0 + e->rows);
+  const int G = hi > lo ? group_queue_slots(e, 1, nk, L.p2) : 0;
+  if (G == 0) {
+    for (int k = 0; k < nk; ++k)
+      if (int rc = answer_mp_locked(e, L, d_keys + (size_t)k * key_stride, thread_num, num_threads,
+                                    d_result + (size_t)k * out_bytes, s))
+        return rc;
+    return PIR_OK;
+  }
+  if (int rc = ensure_group_queue(e, hi - lo, G)) return rc;
+  const int W = G * e->nrp;
+  return answer_group_queue(e, nk, G, 9, lo - p0, hi - lo, d_result, s,
+                            [&](int q0, int ng, uint8_t* d_cb, hipStream_t st) {
+                              return pir::launch_mp_shares_g(L, d_keys + (size_t)q0 * key_stride,
+                                                             key_stride, ng, W, e->nrp, lo, hi,
+                                                             d_cb, e->num_cus, st);
+                            });
+}
+
+uint64_t mp_stage_stride(const pir::MpLayout& L) { return (L.eval_bytes + 15) & ~15ull; }
+
+// a validated layout's queue from device keys of any alignment and stride: keys the share
+// kernels cannot read as 16-byte words go through the aligned staging buffer
+int answer_layout_queue_dev(pir_engine* e, const pir::MpLayout& L, const uint8_t* d_keys,
+                            uint64_t key_stride, int nk, int thread_num, int num_threads,
+                            uint8_t* d_result, void* stream) {
+  if (nk > 1 && key_stride < L.eval_bytes)
+    return fail(PIR_EINVAL, "key_stride %llu < the %llu bytes the evaluation reads",
+                (unsigned long long)key_stride, (unsigned long long)L.eval_bytes);
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = ws_acquire(e, s)) return rc;
+  e->gq_key_bytes = std::max(e->gq_key_bytes, L.eval_bytes);
+  if (L.eval_bytes && (((uintptr_t)d_keys & 15) || (nk > 1 && (key_stride & 15)))) {
+    const uint64_t st = mp_stage_stride(L);
+    if (int rc = ensure_buf(&e->d_mpkey, &e->mpkey_cap, (size_t)nk * st)) return rc;
+    HIP_TRY(hipMemcpy2DAsync(e->d_mpkey, st, d_keys, nk > 1 ? key_stride : st, L.eval_bytes, nk,
+                             hipMemcpyDeviceToDevice, s));
+    d_keys = e->d_mpkey;
+    key_stride = st;
+  }
+  return ws_release(e, s, answer_mp_queue_locked(e, L, d_keys, key_stride, nk, thread_num,
+                                                 num_threads, d_result, s));
+}
+
+// ... and from host keys key_bytes apart, answers copied back to host memory
+int answer_layout_queue_host(pir_engine* e, const pir::MpLayout& L, const uint8_t* keys,
+                             uint64_t key_bytes, int nk, int thread_num, int num_threads,
+                             uint8_t* results, const char* what) {
+  if (key_bytes < L.eval_bytes)
+    return fail(PIR_EINVAL, "%s key of %llu bytes; the evaluation reads %llu", what,
+                (unsigned long long)key_bytes, (unsigned long long)L.eval_bytes);
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  const size_t rb = (size_t)nk * e->cfg.num_rounds * e->cfg.record_bytes;
+  const uint64_t st = std::max<uint64_t>(16, mp_stage_stride(L));
+  if (int rc = ws_acquire(e, e->stream)) return rc;
+  e->gq_key_bytes = std::max(e->gq_key_bytes, L.eval_bytes);
+  int rc = ensure_buf(&e->d_mpkey, &e->mpkey_cap, (size_t)nk * st);
+  if (!rc) rc = ensure_buf(&e->d_shamir_res, &e->shamir_res_cap, rb);
+  if (rc) return rc;
+  if (L.eval_bytes)
+    HIP_TRY(hipMemcpy2DAsync(e->d_mpkey, st, keys, key_bytes, L.eval_bytes, nk,
+                             hipMemcpyHostToDevice, e->stream));
+  rc = ws_release(e, e->stream, answer_mp_queue_locked(e, L, e->d_mpkey, st, nk, thread_num,
+                                                       num_threads, e->d_shamir_res, e->stream));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(results, e->d_shamir_res, rb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return PIR_OK;
+}
+
+int check_queue_args(const void* e, int num_keys, const void* keys, const void* results) {
+  if (!e) return fail(PIR_EINVAL, "null argument");
+  if (num_keys < 0) return fail(PIR_EINVAL, "a queue of %d keys", num_keys);
+  if (num_keys > 0 && (!keys || !results)) return fail(PIR_EINVAL, "null argument");
+  return PIR_OK;
 }
 
 // a validated sqrt(N) layout's answer from a device key (any alignment)
@@ -1492,6 +1695,12 @@ int pir_engine_create(const pir_engine_config* cfg, pir_engine_t** out) {
     if (ws && ws[0]) e->wd_share = std::max(0, std::min(2, atoi(ws)));
     const char* wg = getenv("PIR_WD_G");
     if (wg && wg[0]) e->wd_group = atoi(wg) >= 8 ? 8 : (atoi(wg) >= 4 ? 4 : 2);
+    // $PIR_GQ_SHARE / $PIR_GQ_G: queued explicit-coefficient and sqrt(N) DPF keys per shard pass
+    // (group_queue_slots)
+    const char* gs = getenv("PIR_GQ_SHARE");
+    if (gs && gs[0]) e->gq_share = std::max(0, std::min(2, atoi(gs)));
+    const char* gg = getenv("PIR_GQ_G");
+    if (gg && gg[0]) e->gq_group = atoi(gg) >= 8 ? 8 : (atoi(gg) >= 4 ? 4 : 2);
     const char* bk = getenv("PIR_BATCH_KLAST");
     if (bk) e->batch_k_last = std::max(1, std::min(12, atoi(bk)));
     const int tile = pir::fused_tile(c.num_rounds, e->pitch, e->rows, e->num_cus);
@@ -2442,6 +2651,136 @@ int pir_engine_answer_cd(pir_engine_t* e, const uint8_t* key, uint64_t key_bytes
   if (int rc = check_cd(e, num_cd_keys_needed, num_cd_keys, thread_num, num_threads, &L)) return rc;
   return answer_layout_host(e, L, key, key_bytes, thread_num, num_threads, result,
                             "covering-design");
+}
+
+int pir_engine_answer_coefs_queue_dev(pir_engine_t* e, const uint8_t* d_coefs, uint64_t coef_pitch,
+                                      uint64_t key_stride, int num_keys, uint64_t row0,
+                                      uint64_t nrows, uint8_t* d_result, void* stream) {
+  if (int rc = check_queue_args(e, num_keys, d_coefs, d_result)) return rc;
+  if (int rc = check_rows(e, row0, nrows)) return rc;
+  const auto& c = e->cfg;
+  if (c.num_rounds > 1 && coef_pitch < row0 + nrows)
+    return fail(PIR_EINVAL, "coef_pitch %llu < %llu rows", (unsigned long long)coef_pitch,
+                (unsigned long long)(row0 + nrows));
+  if (num_keys > 1 && key_stride < (uint64_t)(c.num_rounds - 1) * coef_pitch + row0 + nrows)
+    return fail(PIR_EINVAL, "key_stride %llu < the %d vectors of one key",
+                (unsigned long long)key_stride, c.num_rounds);
+  if (num_keys == 0) return PIR_OK;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(c.device));
+  hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = ws_acquire(e, s)) return rc;
+  return ws_release(e, s, answer_coefs_queue_locked(e, d_coefs + row0, coef_pitch, key_stride,
+                                                    num_keys, group_queue_slots(e, 0, num_keys),
+                                                    row0, nrows, d_result, s));
+}
+
+int pir_engine_answer_coefs_queue(pir_engine_t* e, const uint8_t* const* coefs, int num_keys,
+                                  uint64_t row0, uint64_t nrows, uint8_t* results) {
+  if (int rc = check_queue_args(e, num_keys, coefs, results)) return rc;
+  if (int rc = check_rows(e, row0, nrows)) return rc;
+  const auto& c = e->cfg;
+  for (int v = 0; v < num_keys * c.num_rounds && nrows; ++v)
+    if (!coefs[v]) return fail(PIR_EINVAL, "null coefficient vector %d", v);
+  if (num_keys == 0) return PIR_OK;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(c.device));
+  const size_t out_bytes = (size_t)c.num_rounds * c.record_bytes;
+  if (int rc = ws_acquire(e, e->stream)) return rc;
+  // one group's vectors are staged at a time (16-byte aligned rows: the group kernel's wide
+  // loads): G num_rounds <= 8 vectors shared, one key's vectors unshared
+  const int G = nrows ? group_queue_slots(e, 0, num_keys) : 0;
+  const int per = G ? G : 1, ngroups = (num_keys + per - 1) / per;
+  const size_t vp = ((size_t)nrows + 15) & ~(size_t)15, ks = vp * c.num_rounds;
+  int rc = ensure_buf(&e->d_coef_stage, &e->coef_stage_cap, std::max<size_t>(16, ks * per));
+  if (!rc) rc = ensure_buf(&e->d_shamir_res, &e->shamir_res_cap, out_bytes * num_keys);
+  if (rc) return rc;
+  for (int q0 = 0, j = 0, ng = 0; q0 < num_keys; q0 += ng, ++j) {
+    ng = num_keys / ngroups + (j < num_keys % ngroups ? 1 : 0);
+    for (int v = 0; v < ng * c.num_rounds && nrows; ++v)  // only the rows answered travel
+      HIP_TRY(hipMemcpyAsync(e->d_coef_stage + (size_t)v * vp, coefs[q0 * c.num_rounds + v] + row0,
+                             nrows, hipMemcpyHostToDevice, e->stream));
+    rc = answer_coefs_queue_locked(e, e->d_coef_stage, vp, ks, ng, G, row0, nrows,
+                                   e->d_shamir_res + (size_t)q0 * out_bytes, e->stream);
+    if (rc) return rc;
+  }
+  if (int rc2 = ws_release(e, e->stream, PIR_OK)) return rc2;
+  HIP_TRY(hipMemcpyAsync(results, e->d_shamir_res, out_bytes * num_keys, hipMemcpyDeviceToHost,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return PIR_OK;
+}
+
+int pir_engine_answer_mp_queue_dev(pir_engine_t* e, const uint8_t* d_keys, uint64_t key_stride,
+                                   int num_keys, int p, int t, int thread_num, int num_threads,
+                                   uint8_t* d_result, void* stream) {
+  if (int rc = check_queue_args(e, num_keys, d_keys, d_result)) return rc;
+  pir::MpLayout L;
+  if (int rc = check_mp(e, p, t, thread_num, num_threads, &L)) return rc;
+  if (num_keys == 0) return PIR_OK;
+  return answer_layout_queue_dev(e, L, d_keys, key_stride, num_keys, thread_num, num_threads,
+                                 d_result, stream);
+}
+
+int pir_engine_answer_mp_queue(pir_engine_t* e, const uint8_t* keys, uint64_t key_bytes,
+                               int num_keys, int p, int t, int thread_num, int num_threads,
+                               uint8_t* results) {
+  if (int rc = check_queue_args(e, num_keys, keys, results)) return rc;
+  pir::MpLayout L;
+  if (int rc = check_mp(e, p, t, thread_num, num_threads, &L)) return rc;
+  if (num_keys == 0) return PIR_OK;
+  return answer_layout_queue_host(e, L, keys, key_bytes, num_keys, thread_num, num_threads, results,
+                                  "multiparty");
+}
+
+int pir_engine_answer_cd_queue_dev(pir_engine_t* e, const uint8_t* d_keys, uint64_t key_stride,
+                                   int num_keys, int num_cd_keys_needed, int num_cd_keys,
+                                   int thread_num, int num_threads, uint8_t* d_result,
+                                   void* stream) {
+  if (int rc = check_queue_args(e, num_keys, d_keys, d_result)) return rc;
+  pir::MpLayout L;
+  if (int rc = check_cd(e, num_cd_keys_needed, num_cd_keys, thread_num, num_threads, &L)) return rc;
+  if (num_keys == 0) return PIR_OK;
+  return answer_layout_queue_dev(e, L, d_keys, key_stride, num_keys, thread_num, num_threads,
+                                 d_result, stream);
+}
+
+int pir_engine_answer_cd_queue(pir_engine_t* e, const uint8_t* keys, uint64_t key_bytes,
+                               int num_keys, int num_cd_keys_needed, int num_cd_keys,
+                               int thread_num, int num_threads, uint8_t* results) {
+  if (int rc = check_queue_args(e, num_keys, keys, results)) return rc;
+  pir::MpLayout L;
+  if (int rc = check_cd(e, num_cd_keys_needed, num_cd_keys, thread_num, num_threads, &L)) return rc;
+  if (num_keys == 0) return PIR_OK;
+  return answer_layout_queue_host(e, L, keys, key_bytes, num_keys, thread_num, num_threads, results,
+                                  "covering-design");
+}
+
+int pir_engine_reserve_group_queue(pir_engine_t* e, int num_keys) {
+  if (!e || num_keys < 1) return fail(PIR_EINVAL, "bad argument");
+  const auto& c = e->cfg;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(c.device));
+  // the single answers an unshared queue runs: the explicit-coefficient scan, k_query's sqrt(N) mode
+  pir::ScanShape sh = pir::make_scan_shape(e->rows, e->pitch, c.num_rounds, e->num_cus);
+  size_t slab = (size_t)sh.grid.x * sh.grid.y * sh.slab_bytes;
+  const pir::QueryPlan qp = pir::make_query_plan(c.log_num_records, c.log_num_partitions, 2,
+                                                 c.num_rounds, e->pitch, e->num_cus);
+  if (qp.tile) slab = std::max(slab, pir::query_slab_bytes(qp));
+  int rc = ensure_slabs(e, slab);
+  // a shared queue at the widest share row (rows x 8 bytes whatever $PIR_GQ_G says)
+  if (!rc && e->nrp <= 4) rc = ensure_group_queue(e, e->rows, 8 / e->nrp);
+  // the host forms' staging: one group's vectors, the keys, the results; the device form's
+  // staging of unaligned keys, for the longest key a queue of this engine has brought so far
+  const size_t vp = ((size_t)e->rows + 15) & ~(size_t)15;
+  if (!rc) rc = ensure_buf(&e->d_coef_stage, &e->coef_stage_cap, vp * std::max(8, c.num_rounds));
+  if (!rc)
+    rc = ensure_buf(&e->d_shamir_res, &e->shamir_res_cap,
+                    (size_t)num_keys * c.num_rounds * c.record_bytes);
+  if (!rc && e->gq_key_bytes)
+    rc = ensure_buf(&e->d_mpkey, &e->mpkey_cap,
+                    (size_t)num_keys * ((e->gq_key_bytes + 15) & ~15ull));
+  return rc;
 }
 
 int pir_engine_answer_slice(pir_engine_t* e, const uint8_t* key, int thread_num, int num_threads,

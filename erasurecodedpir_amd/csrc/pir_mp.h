@@ -39,6 +39,12 @@ bool cd_layout(int n, int q_needed, int num_cd_keys, MpLayout* out);
 // (row-aligned or 16-aligned bounds not required); d_key: the raw key, eval_bytes long
 hipError_t launch_mp_shares(const MpLayout& L, const uint8_t* d_key, uint64_t rec_lo,
                             uint64_t rec_hi, int nrp, uint8_t* d_c, int num_cus, hipStream_t s);
+// The same for a group of ng queued keys of one layout, d_keys + g * key_stride (both multiples
+// of 16): d_c[(r - rec_lo) * W + g * nrp + a] = share[a][r] of key g, zero for g >= ng and a >=
+// nrk.  W = 2, 4 or 8 bytes per record, W >= ng * nrp; nrp = 1, 2 or 4; d_c 16-byte aligned.
+hipError_t launch_mp_shares_g(const MpLayout& L, const uint8_t* d_keys, uint64_t key_stride, int ng,
+                              int W, int nrp, uint64_t rec_lo, uint64_t rec_hi, uint8_t* d_c,
+                              int num_cus, hipStream_t s);
 // this translation unit's copy of the AES table (once per device, before the first launch)
 
 }  // namespace pir

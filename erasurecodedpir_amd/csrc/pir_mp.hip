@@ -10,6 +10,7 @@
 // the tree DPF's, so the answer stays bound by the shard scan's HBM stream.
 #include "pir_aes.h"
 #include "pir_mp.h"
+#include "pir_transpose.h"
 
 #include <math.h>
 
@@ -178,6 +179,110 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_shares(const uint8_t* __restr
   }
 }
 
+// k_mp_shares for a group of queued keys: ng <= W / NRP keys, key_stride bytes apart (a multiple
+// of 16), one layout.  Byte g NRP + a of a record's W-byte share row is share a of key slot g
+// (zero for g >= ng and a >= nrk).  The lane's item, AES schedule and fold are k_mp_shares'; the
+// slot loop runs the AES code once per (seed, slot) and folds the block into acc[g NRP + a][r]
+// through per-byte-slot masks, so every accumulator index is a compile-time constant (W R uint4
+// of accumulators: 32 VGPRs at W = 8, R = 1).  Each counter block's W accumulators are byte-
+// transposed in registers (pir_transpose.h) and leave as W 16-byte stores.
+template <int W, int NRP, int R>
+__global__ __launch_bounds__(kMpThreads) void k_mp_shares_g(const uint8_t* __restrict__ keys,
+                                                            uint64_t key_stride, int ng,
+                                                            MpLayout L, uint64_t rec_lo,
+                                                            uint64_t rec_hi,
+                                                            uint8_t* __restrict__ d_c) {
+  __shared__ uint32_t lds_tab[kTablesBytes / 4];
+  load_tables_n<kMpThreads>(lds_tab);
+  __syncthreads();
+  const Tab T(lds_tab);
+  const uint64_t I = L.mu < 16ull * R ? L.mu : 16ull * R;  // records per item
+  const int wb = (int)(I < 16 ? I : 16);                    // bytes used per CTR block
+  const uint64_t it0 = rec_lo / I, it1 = (rec_hi + I - 1) / I;
+  const bool cw_al = (L.cw_off & 15) == 0 && (L.mu & 15) == 0;
+  const uint64_t row_tog = (uint64_t)L.nu * L.p2;
+  for (uint64_t it = it0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; it < it1;
+       it += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t g0 = it * I, i = g0 / L.mu, x0 = g0 - i * L.mu;
+    const uint32_t b0 = (uint32_t)(x0 >> 4);
+    uint4 acc[W][R];
+#pragma unroll
+    for (int b = 0; b < W; ++b)
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[b][r] = make_uint4(0, 0, 0, 0);
+    for (int g = 0; g < ng; ++g) {
+      const uint8_t* key = keys + (uint64_t)g * key_stride;
+      for (uint32_t j = 0; j < L.p2; ++j) {
+        uint32_t m[NRP];
+        uint32_t any = 0;
+#pragma unroll
+        for (int a = 0; a < NRP; ++a) {
+          m[a] = (a < L.nrk && key[L.tog_off + a * row_tog + i * L.p2 + j]) ? ~0u : 0u;
+          any |= m[a];
+        }
+        if (!any) continue;
+        const uint4 seed = *reinterpret_cast<const uint4*>(key + i * 16ull * L.p2 + 16ull * j);
+        uint4 ks[R];
+        aes_ctr_row<R, 4>(T, seed, ks, __builtin_bswap32(b0));
+        const uint64_t cwb = L.cw_off + (uint64_t)j * L.mu + 16ull * b0;
+        uint32_t mb[W];  // the mask of byte slot b: m[b % NRP] in key slot g, zero elsewhere
+#pragma unroll
+        for (int b = 0; b < W; ++b) mb[b] = (b / NRP == g) ? m[b % NRP] : 0u;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const uint4 v = xor4(ks[r], load_cw(key, cwb + 16ull * r, cw_al, wb));
+#pragma unroll
+          for (int b = 0; b < W; ++b) acc[b][r] = xor4(acc[b][r], and4(v, mb[b]));
+        }
+      }
+    }
+    // records g0 + 16 r + k  ->  d_c[(record - rec_lo) * W + b]
+    const bool full = wb == 16 && g0 >= rec_lo && g0 + I <= rec_hi && ((g0 - rec_lo) & 15) == 0;
+    if (full) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        uint4 v[W], o[W];
+#pragma unroll
+        for (int b = 0; b < W; ++b) v[b] = acc[b][r];
+        tr_records<W>(v, o);
+        uint4* dst = reinterpret_cast<uint4*>(d_c + (g0 + 16ull * r - rec_lo) * W);
+#pragma unroll
+        for (int q = 0; q < W; ++q) dst[q] = o[q];
+      }
+    } else {  // range edges, rows shorter than 16 records: byte stores
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          const uint64_t rec = g0 + 16ull * r + k;
+          if (k >= wb || rec < rec_lo || rec >= rec_hi) continue;
+#pragma unroll
+          for (int b = 0; b < W; ++b) d_c[(rec - rec_lo) * W + b] = (uint8_t)tr_byte(acc[b][r], k);
+        }
+    }
+  }
+}
+
+template <int W, int NRP>
+hipError_t launch_g(const MpLayout& L, const uint8_t* d_keys, uint64_t key_stride, int ng,
+                    uint64_t lo, uint64_t hi, uint8_t* d_c, int num_cus, hipStream_t s) {
+  // counter blocks per lane, wide rows: at most 8 accumulator vectors, and two blocks (four, at
+  // W = 2, spill 20 VGPRs of AES state under the 128 of a 1024-thread workgroup)
+  constexpr int RW = W >= 8 ? 1 : 2;
+  const bool wide = RW > 1 && L.mu >= 16ull * RW;
+  const uint64_t I = wide ? 16ull * RW : std::min<uint64_t>(L.mu, 16);
+  const uint64_t items = (hi + I - 1) / I - lo / I;
+  const unsigned grid = (unsigned)std::max<uint64_t>(
+      1, std::min<uint64_t>((items + kMpThreads - 1) / kMpThreads, (uint64_t)num_cus * 2));
+  if (wide)
+    hipLaunchKernelGGL((k_mp_shares_g<W, NRP, RW>), dim3(grid), dim3(kMpThreads), 0, s, d_keys,
+                       key_stride, ng, L, lo, hi, d_c);
+  else
+    hipLaunchKernelGGL((k_mp_shares_g<W, NRP, 1>), dim3(grid), dim3(kMpThreads), 0, s, d_keys,
+                       key_stride, ng, L, lo, hi, d_c);
+  return hipGetLastError();
+}
+
 template <int NRP>
 hipError_t launch_nrp(const MpLayout& L, const uint8_t* d_key, uint64_t lo, uint64_t hi,
                       uint8_t* d_c, int num_cus, hipStream_t s) {
@@ -210,6 +315,25 @@ hipError_t launch_mp_shares(const MpLayout& L, const uint8_t* d_key, uint64_t re
     case 16: return launch_nrp<16>(L, d_key, rec_lo, rec_hi, d_c, num_cus, s);
     default: return hipErrorInvalidValue;
   }
+}
+
+hipError_t launch_mp_shares_g(const MpLayout& L, const uint8_t* d_keys, uint64_t key_stride, int ng,
+                              int W, int nrp, uint64_t rec_lo, uint64_t rec_hi, uint8_t* d_c,
+                              int num_cus, hipStream_t s) {
+  if (rec_hi <= rec_lo || L.nu == 0) return hipSuccess;
+  if (nrp < L.nrk || rec_hi > L.nu * L.mu || ng < 1 || ng * nrp > W || (key_stride & 15) ||
+      ((uintptr_t)d_keys & 15) || ((uintptr_t)d_c & 15))
+    return hipErrorInvalidValue;
+#define PIR_MPG(WW, NN) \
+  if (W == WW && nrp == NN) return launch_g<WW, NN>(L, d_keys, key_stride, ng, rec_lo, rec_hi, d_c, num_cus, s)
+  PIR_MPG(2, 1);
+  PIR_MPG(4, 1);
+  PIR_MPG(8, 1);
+  PIR_MPG(4, 2);
+  PIR_MPG(8, 2);
+  PIR_MPG(8, 4);
+#undef PIR_MPG
+  return hipErrorInvalidValue;
 }
 
 }  // namespace pir

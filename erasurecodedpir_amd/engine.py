@@ -385,6 +385,81 @@ class Engine:
                                                  thread_num, num_threads, d_result, stream),
               "answer_cd_dev")
 
+    # -- queues of explicit-coefficient, multiparty and covering-design queries ----------------
+    def answer_coefs_queue(self, coefs, row0=0, nrows=None):
+        """A queue of independent explicit-coefficient queries over the rows [row0, row0 +
+        nrows): coefs is (K, num_rounds, rows) uint8 -> (K, num_rounds, record_bytes), row k what
+        answer_coefs gives for coefs[k].  Where it measured faster the queued keys share passes
+        over the shard (8 / nrp keys per read of it; $PIR_GQ_SHARE, $PIR_GQ_G:
+        include/pir_engine.h), else each key has its own answer, back to back."""
+        nk = len(coefs)
+        c = np.ascontiguousarray(np.asarray(coefs, np.uint8).reshape(nk, self.num_rounds, -1)) \
+            if nk else np.zeros((0, self.num_rounds, self.num_rows), np.uint8)
+        nrows = c.shape[2] - row0 if nrows is None else nrows
+        ptrs = (ctypes.c_void_p * max(1, nk * self.num_rounds))(
+            *[c[k, a].ctypes.data for k in range(nk) for a in range(self.num_rounds)])
+        out = np.empty((nk, self.num_rounds, self.record_bytes), np.uint8)
+        check(self._lib.pir_engine_answer_coefs_queue(self._h, ptrs, nk, row0, nrows,
+                                                      out.ctypes.data_as(ctypes.c_void_p)),
+              "pir_engine_answer_coefs_queue")
+        return out
+
+    def answer_coefs_queue_dev(self, d_coefs, coef_pitch, key_stride, num_keys, row0, nrows,
+                               d_result, stream=None):
+        check(self._lib.pir_engine_answer_coefs_queue_dev(self._h, d_coefs, coef_pitch, key_stride,
+                                                          num_keys, row0, nrows, d_result, stream),
+              "answer_coefs_queue_dev")
+
+    def _queue_keys(self, keys, what):
+        ks = [np.frombuffer(bytes(k), np.uint8) if not isinstance(k, np.ndarray)
+              else np.asarray(k, np.uint8).reshape(-1) for k in keys]
+        if any(k.size != ks[0].size for k in ks):
+            raise _lib.PirError("%s: keys of different lengths" % what)
+        k = np.ascontiguousarray(np.concatenate(ks)) if ks else np.zeros(1, np.uint8)
+        return k, len(ks), (ks[0].size if ks else 0)
+
+    def answer_mp_queue(self, keys, p, t, thread_num=0, num_threads=1):
+        """A queue of independent multiparty sqrt(N) DPF queries (keys of one length) over one
+        thread slice -> (K, num_rounds, record_bytes), row k what answer_mp gives for keys[k];
+        sharing as answer_coefs_queue."""
+        k, nk, kb = self._queue_keys(keys, "answer_mp_queue")
+        out = np.empty((nk, self.num_rounds, self.record_bytes), np.uint8)
+        check(self._lib.pir_engine_answer_mp_queue(self._h, k.ctypes.data_as(ctypes.c_void_p), kb,
+                                                   nk, p, t, thread_num, num_threads,
+                                                   out.ctypes.data_as(ctypes.c_void_p)),
+              "pir_engine_answer_mp_queue")
+        return out
+
+    def answer_mp_queue_dev(self, d_keys, key_stride, num_keys, p, t, d_result, thread_num=0,
+                            num_threads=1, stream=None):
+        check(self._lib.pir_engine_answer_mp_queue_dev(self._h, d_keys, key_stride, num_keys, p, t,
+                                                       thread_num, num_threads, d_result, stream),
+              "answer_mp_queue_dev")
+
+    def answer_cd_queue(self, keys, num_cd_keys_needed, num_cd_keys, thread_num=0, num_threads=1):
+        """A queue of independent covering-design sqrt(N) DPF queries -> (K, num_rounds,
+        record_bytes), row k what answer_cd gives for keys[k]; sharing as answer_coefs_queue."""
+        k, nk, kb = self._queue_keys(keys, "answer_cd_queue")
+        out = np.empty((nk, self.num_rounds, self.record_bytes), np.uint8)
+        check(self._lib.pir_engine_answer_cd_queue(self._h, k.ctypes.data_as(ctypes.c_void_p), kb,
+                                                   nk, num_cd_keys_needed, num_cd_keys, thread_num,
+                                                   num_threads,
+                                                   out.ctypes.data_as(ctypes.c_void_p)),
+              "pir_engine_answer_cd_queue")
+        return out
+
+    def answer_cd_queue_dev(self, d_keys, key_stride, num_keys, num_cd_keys_needed, num_cd_keys,
+                            d_result, thread_num=0, num_threads=1, stream=None):
+        check(self._lib.pir_engine_answer_cd_queue_dev(self._h, d_keys, key_stride, num_keys,
+                                                       num_cd_keys_needed, num_cd_keys, thread_num,
+                                                       num_threads, d_result, stream),
+              "answer_cd_queue_dev")
+
+    def reserve_group_queue(self, num_keys):
+        """Pre-size the work buffers for explicit-coefficient and sqrt(N) DPF queues of up to
+        num_keys keys (no allocation inside later queue calls)."""
+        check(self._lib.pir_engine_reserve_group_queue(self._h, num_keys), "reserve_group_queue")
+
     def eval_all(self, key):
         """(num_rounds, rows) DPF shares dataShare[a][i]."""
         k, kp = self._check_key(key)

@@ -34,6 +34,10 @@
  *   pir_engine_answer_cd[_dev]       runCDQueryThread (evalAllCDThread)     server.cpp:443-492,
  *                                                                 multiparty_dpf.cpp:617-690
  *   pir_engine_cd_key_len            calcCDDPFKeyLength                     utils.cpp:118-129
+ *   pir_engine_answer_coefs_queue[_dev]     K answers of one mode, 8 / nrp keys per read of the
+ *   pir_engine_answer_mp_queue[_dev]        shard (no counterpart: the reference answers one key)
+ *   pir_engine_answer_cd_queue[_dev]
+ *   pir_engine_reserve_group_queue
  *   pir_engine_key_len               calcOptimizedDPFTreeKeyLength          utils.cpp:85-90
  *   pir_comm_* + partitions          (new) split-shard across GPUs, XOR all-reduce over RCCL
  */
@@ -276,6 +280,54 @@ int pir_engine_answer_cd_dev(pir_engine_t *e, const uint8_t *d_key, int num_cd_k
                              void *stream);
 /* calcCDDPFKeyLength(p, n, t, q, c) (p and t unused there too); 0 for no layout */
 int pir_engine_cd_key_len(int p, int n, int t, int num_cd_keys_needed, int num_cd_keys);
+/* ---- queues of explicit-coefficient, multiparty and covering-design queries ----
+ * num_keys independent queries of one mode over one range or thread slice; results num_keys x
+ * num_rounds x record_bytes back to back, result k byte for byte what the single call
+ * (pir_engine_answer_coefs / _mp / _cd [_dev]) gives for key k with the same range or slice.  The
+ * refusals are those of the single calls; num_keys < 0 and, with num_keys > 0, null pointers are
+ * PIR_EINVAL; num_keys == 0 touches nothing; an empty range, an empty slice or nu == 0 zeroes
+ * every result.  A shared queue goes into ceil(K / G) groups of as equal sizes as possible (20 ->
+ * 7 + 7 + 6), G = 8 / nrp key slots per pass (nrp: num_rounds rounded up to a power of two; a
+ * queue of an engine with nrp > 4 has one slot and runs unshared); one kernel writes a group's
+ * W = G nrp share bytes of every record (k_interleave_coefs_g from the groups' vectors,
+ * k_mp_shares_g from its sqrt(N) keys) and one W-round scan reads the shard once for the group.
+ * $PIR_GQ_SHARE, read at engine creation: 0 never shares (the single answers back to back on the
+ * stream), unset or 1 follows the measured policy (Queued Hollanti, multiparty and CD
+ * queries), 2 shares every queue of two or more keys that has two or more slots; $PIR_GQ_G
+ * overrides the slots per pass (2, 4 or 8, at most 8 / nrp).  A partition engine shares passes
+ * over its partition; with a communicator attached the queue runs the single answers back to
+ * back, each with its own exchange.
+ * coefs_queue_dev: key k's round a coefficient of engine row r at d_coefs[k * key_stride + a *
+ * coef_pitch + r] (any alignment; 16-byte aligned vectors are read fastest).  coefs_queue: coefs
+ * holds num_keys * num_rounds host pointers, key-major (key k's round a at coefs[k * num_rounds +
+ * a]), each a vector over the engine's rows; one group's vectors are staged at a time.
+ * mp / cd _queue_dev: keys key_stride bytes apart (>= the bytes the evaluation reads), any
+ * alignment and stride (keys whose address or stride is no multiple of 16 are copied to an aligned
+ * staging buffer first, as the single answer does for one key).  mp / cd _queue: host keys
+ * key_bytes apart (>= the bytes the evaluation reads). */
+int pir_engine_answer_coefs_queue_dev(pir_engine_t *e, const uint8_t *d_coefs, uint64_t coef_pitch,
+                                      uint64_t key_stride, int num_keys, uint64_t row0,
+                                      uint64_t nrows, uint8_t *d_result, void *stream);
+int pir_engine_answer_coefs_queue(pir_engine_t *e, const uint8_t *const *coefs, int num_keys,
+                                  uint64_t row0, uint64_t nrows, uint8_t *results);
+int pir_engine_answer_mp_queue_dev(pir_engine_t *e, const uint8_t *d_keys, uint64_t key_stride,
+                                   int num_keys, int p, int t, int thread_num, int num_threads,
+                                   uint8_t *d_result, void *stream);
+int pir_engine_answer_mp_queue(pir_engine_t *e, const uint8_t *keys, uint64_t key_bytes,
+                               int num_keys, int p, int t, int thread_num, int num_threads,
+                               uint8_t *results);
+int pir_engine_answer_cd_queue_dev(pir_engine_t *e, const uint8_t *d_keys, uint64_t key_stride,
+                                   int num_keys, int num_cd_keys_needed, int num_cd_keys,
+                                   int thread_num, int num_threads, uint8_t *d_result,
+                                   void *stream);
+int pir_engine_answer_cd_queue(pir_engine_t *e, const uint8_t *keys, uint64_t key_bytes,
+                               int num_keys, int num_cd_keys_needed, int num_cd_keys,
+                               int thread_num, int num_threads, uint8_t *results);
+/* pre-size everything these queues touch for up to num_keys keys over the whole shard (the share
+ * buffer of rows x 8 bytes, the slabs, the group answer, the host forms' staging, and the staging
+ * of unaligned device keys for the longest sqrt(N) key a queue of this engine has brought so far),
+ * so that a later queue call allocates nothing */
+int pir_engine_reserve_group_queue(pir_engine_t *e, int num_keys);
 /* DPF shares of this engine's rows: out[a*R + i] (dataShare[a][i]) */
 int pir_engine_eval_all(pir_engine_t *e, const uint8_t *key, uint8_t *out);
 
@@ -340,7 +392,10 @@ int pir_engine_memcpy_d2h(pir_engine_t *e, void *h_dst, const void *d_src, size_
  * answers (fused = 7): launch = start -> the answer zeroed, scan = the two passes, reduce = 0.
  * A shared Woodruff queue (fused = 8) has one event set: launch = start -> the first coefficient
  * kernel, scan = that -> the end of the last group's scan, reduce = the last group's k_reduce;
- * an unshared queue records what its single answers record. */
+ * an unshared queue records what its single answers record.  A shared queue of
+ * explicit-coefficient, multiparty or covering-design queries (fused = 9) has the same one event
+ * set with its share kernel in the coefficient kernel's place; the single answers of these modes
+ * record none. */
 typedef struct {
     char name[32];
     float ms;
