@@ -88,6 +88,7 @@ PROTOTYPES = {
     "pir_engine_encode_within_rows": (_I, [_P, _P, _U64, ctypes.c_uint32, _I, _I]),
     "pir_engine_fill_shard_random": (_I, [_P, _U64]),
     "pir_engine_encode_across_dev": (_I, [_P, _P, _U64, _U64, _I]),
+    "pir_engine_encode_across_synthetic_mac": (_I, [_P, _U64, _I, _P]),
     "pir_engine_encode_within_dev": (_I, [_P, _P, _U64, _U64, ctypes.c_uint32, _I, _I]),
     "pir_engine_get_shard_row": (_I, [_P, _U64, _P]),
     "pir_engine_get_shard": (_I, [_P, _U64, _U64, _P]),
@@ -141,6 +142,7 @@ PROTOTYPES = {
     "pir_engine_alloc_dev": (_I, [_P, _SZ, ctypes.POINTER(_P)]),
     "pir_engine_free_dev": (_I, [_P, _P]),
     "pir_engine_set_party_index": (_I, [_P, _I]),
+    "pir_engine_fill_random_dev": (_I, [_P, _P, _SZ, _U64]),
     "pir_engine_memcpy_h2d": (_I, [_P, _P, _P, _SZ]),
     "pir_engine_memcpy_d2h": (_I, [_P, _P, _P, _SZ]),
     "pir_engine_set_profiling": (_I, [_P, _I]),
@@ -154,6 +156,9 @@ PROTOTYPES = {
     # pir_client.h
     "pir_gen_keys": (_I, [_I, _I, _U64, _P, _I, _I, _P, _P]),
     "pir_final_cw": (None, [_I, _I, _I, _P]),
+    "pir_mac_files_dev": (_I, [_I, _P, _U64, _U64, _U32, _P, _P, _U64, _P]),
+    "pir_mac_files_rows": (_I, [_I, _P, _U64, _U32, _P]),
+    "pir_mac_check": (_I, [_P, _U32, _P]),
     # pir_server.h (reference names)
     "setSystemParams": (None, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "freeParams": (None, []),
@@ -233,6 +238,7 @@ PROTOTYPES = {
     "runOptShamirDPFQuery": (None, [ctypes.POINTER(CServer), ctypes.POINTER(c_u8_p),
                                     ctypes.POINTER(c_u8_p)]),
     "pirSetDevice": (None, [_I]),
+    "pirClientTagFiles": (None, [ctypes.POINTER(CClient)]),
     "pirServerShardChanged": (None, [ctypes.POINTER(CServer)]),
     "pirServerSyncRows": (None, [ctypes.POINTER(CServer)]),
     "pirRunTreeQueryThreads": (None, [ctypes.POINTER(CServer), ctypes.c_void_p, ctypes.c_int,

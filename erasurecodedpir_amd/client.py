@@ -1,5 +1,6 @@
-"""Client-side helpers (include/pir_client.h): DPF key generation on the GPU and the finalCW
-values of generate_opt_DPF_tree_query (src/c/client.cpp:144-153)."""
+"""Client-side helpers (include/pir_client.h): DPF key generation on the GPU, the finalCW
+values of generate_opt_DPF_tree_query (src/c/client.cpp:144-153) and the CheckMAC record tags
+(HMAC-SHA256 under a 16-byte key, client.cpp:29-31) computed on the GPU."""
 import ctypes
 import os
 
@@ -34,3 +35,62 @@ def gen_keys(n, index, p, nq=1, fcw=None, rho=1, seeds=None, device=0):
                                    seeds.ctypes.data_as(ctypes.c_void_p),
                                    out.ctypes.data_as(ctypes.c_void_p)), "pir_gen_keys")
     return [out[j * kl:(j + 1) * kl].tobytes() for j in range(p)]
+
+
+MAC_BYTES = 32
+
+
+def _key16(key):
+    k = np.frombuffer(bytes(key), np.uint8).copy()
+    if k.size != 16:
+        raise ValueError("the tag key is 16 bytes")
+    return k
+
+
+def mac_files(files2d, payload_bytes, key, device=0):
+    """Tag the rows of a C-contiguous uint8 (num_files, >= payload_bytes + 32) array in place on
+    the GPU: row[payload_bytes : payload_bytes + 32] = HMAC-SHA256(key, row[:payload_bytes])
+    (pir_mac_files_rows: only the payloads go to the device, only the tags come back)."""
+    f = files2d
+    if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 2 and
+            f.flags.c_contiguous and f.flags.writeable):
+        raise ValueError("files2d is a writeable C-contiguous 2-D uint8 array")
+    if payload_bytes < 1 or f.shape[1] < payload_bytes + MAC_BYTES:
+        raise ValueError("rows hold payload_bytes + 32 bytes")
+    n, pitch = f.shape
+    rows = (ctypes.c_void_p * max(1, n))(*[f.ctypes.data + i * pitch for i in range(n)])
+    k = _key16(key)
+    check(_lib.load().pir_mac_files_rows(device, rows, n, payload_bytes,
+                                         k.ctypes.data_as(ctypes.c_void_p)), "pir_mac_files_rows")
+    return f
+
+
+def mac_files_dev(d_files, file_pitch, num_files, payload_bytes, key, d_tags=None, tag_pitch=None,
+                  device=0, stream=None):
+    """pir_mac_files_dev over device memory: d_files / d_tags are device addresses (an
+    Engine.alloc_dev pointer or a torch tensor's data_ptr(), plus any offset).  d_tags=None tags
+    in place (d_files + payload_bytes, the rows' own pitch).  Asynchronous on `stream` (a
+    hipStream_t address; None: the null stream)."""
+    if d_tags is None:
+        d_tags, tag_pitch = int(d_files) + payload_bytes, file_pitch
+    k = _key16(key)
+    check(_lib.load().pir_mac_files_dev(device, ctypes.c_void_p(int(d_files)), file_pitch,
+                                        num_files, payload_bytes,
+                                        k.ctypes.data_as(ctypes.c_void_p),
+                                        ctypes.c_void_p(int(d_tags)), tag_pitch,
+                                        ctypes.c_void_p(stream) if stream else None),
+          "pir_mac_files_dev")
+
+
+def mac_check(record, payload_bytes, key):
+    """True if record[payload_bytes : payload_bytes + 32] is the tag of record[:payload_bytes]
+    (the client's check of a decoded record, benchmark.go:190-207).  Host only."""
+    r = np.frombuffer(bytes(record), np.uint8).copy()
+    if payload_bytes < 1 or r.size < payload_bytes + MAC_BYTES:
+        raise ValueError("the record holds payload_bytes + 32 bytes")
+    k = _key16(key)
+    rc = _lib.load().pir_mac_check(r.ctypes.data_as(ctypes.c_void_p), payload_bytes,
+                                   k.ctypes.data_as(ctypes.c_void_p))
+    if rc < 0:
+        check(rc, "pir_mac_check")
+    return rc == 0

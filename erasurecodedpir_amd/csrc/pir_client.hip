@@ -5,12 +5,22 @@
 // words are formed from the LOSE children, and each party keeps its KEEP child corrected by
 // the CWs its control bits select.  One 64-lane workgroup: 3p <= 51 lanes expand, lane 0
 // forms the CWs, every lane writes key bytes.
+//
+// The CheckMAC record tags (pir_mac_files_dev / _rows / pir_mac_check) are here too: the
+// argument checks and the staging of host rows around k_hmac_sha256_files (pir_mac.hip).
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+
+#include <algorithm>
+#include <functional>
+#include <thread>
+#include <vector>
 
 #include "../../include/pir_client.h"
 #include "../../include/pir_engine.h"
 #include "pir_aes.h"
+#include "pir_mac.h"
 
 namespace pir {
 namespace {
@@ -109,6 +119,15 @@ uint8_t gf_mul_h(uint8_t a, uint8_t b) {
   return r;
 }
 
+// host threads that gather payloads and scatter tags ($PIR_GATHER_THREADS, as the engine's
+// staged copies)
+int host_threads() {
+  if (const char* v = getenv("PIR_GATHER_THREADS")) return std::max(1, atoi(v));
+  int n = (int)std::thread::hardware_concurrency();
+  if (const char* v = getenv("OMP_NUM_THREADS")) n = std::min(n, std::max(1, atoi(v)));
+  return std::max(1, std::min(8, n));
+}
+
 }  // namespace
 }  // namespace pir
 
@@ -155,6 +174,100 @@ int pir_gen_keys(int device, int n, uint64_t index, const uint8_t* fcw, int p, i
   if (d_keys) (void)hipFree(d_keys);
   (void)hipStreamDestroy(s);
   return rc;
+}
+
+int pir_mac_files_dev(int device, const uint8_t* d_files, uint64_t file_pitch, uint64_t num_files,
+                      uint32_t payload_bytes, const uint8_t key[16], uint8_t* d_tags,
+                      uint64_t tag_pitch, void* stream) {
+  if (!d_files || !d_tags || !key || payload_bytes == 0 || file_pitch < payload_bytes ||
+      tag_pitch < PIR_MAC_BYTES)
+    return PIR_EINVAL;
+  if (!num_files) return PIR_OK;
+  if (hipSetDevice(device) != hipSuccess) return PIR_EHIP;
+  return pir::launch_hmac_sha256_files(d_files, file_pitch, num_files, payload_bytes,
+                                       pir::hmac_states(key), d_tags, tag_pitch,
+                                       static_cast<hipStream_t>(stream)) == hipSuccess
+             ? PIR_OK
+             : PIR_EHIP;
+}
+
+int pir_mac_files_rows(int device, uint8_t* const* files, uint64_t num_files,
+                       uint32_t payload_bytes, const uint8_t key[16]) {
+  if (!files || !key || payload_bytes == 0) return PIR_EINVAL;
+  if (!num_files) return PIR_OK;
+  uint64_t m = std::max<uint64_t>(1, (64ull << 20) / payload_bytes);
+  if (const char* v = getenv("PIR_MAC_CHUNK_FILES")) m = std::max<uint64_t>(1, strtoull(v, nullptr, 10));
+  m = std::min(m, num_files);
+  const uint64_t nchunks = (num_files + m - 1) / m;
+  const pir::HmacStates st = pir::hmac_states(key);
+  if (hipSetDevice(device) != hipSuccess) return PIR_EHIP;
+  // chunk c: host threads gather the payloads into pinned h_pay[c & 1]; copy, kernel and the copy
+  // of the tags into pinned h_tag[c & 1] are enqueued; the tags of chunk c - 2 are scattered to
+  // their files once that chunk's event has fired, before its buffers are reused
+  hipStream_t s = nullptr;
+  uint8_t *h_pay[2] = {}, *h_tag[2] = {}, *d_pay[2] = {}, *d_tag[2] = {};
+  hipEvent_t done[2] = {};
+  int rc = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess ? PIR_OK : PIR_EHIP;
+  for (int i = 0; i < 2 && !rc; ++i)
+    if (hipHostMalloc(&h_pay[i], (size_t)m * payload_bytes) != hipSuccess ||
+        hipHostMalloc(&h_tag[i], (size_t)m * PIR_MAC_BYTES) != hipSuccess ||
+        hipMalloc(&d_pay[i], (size_t)m * payload_bytes) != hipSuccess ||
+        hipMalloc(&d_tag[i], (size_t)m * PIR_MAC_BYTES) != hipSuccess ||
+        hipEventCreateWithFlags(&done[i], hipEventDisableTiming) != hipSuccess)
+      rc = PIR_ENOMEM;
+  const int T = pir::host_threads();
+  auto chunk_len = [&](uint64_t c) { return std::min(m, num_files - c * m); };
+  auto on_rows = [&](uint64_t n, const std::function<void(uint64_t)>& fn) {
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; ++t)
+      th.emplace_back([&, t] {
+        for (uint64_t i = n * t / T; i < n * (t + 1) / T; ++i) fn(i);
+      });
+    for (uint64_t i = 0; i < n / T; ++i) fn(i);
+    for (auto& x : th) x.join();
+  };
+  auto scatter = [&](uint64_t c) {  // tags of chunk c -> files
+    const int b = (int)(c & 1);
+    if (hipEventSynchronize(done[b]) != hipSuccess) return PIR_EHIP;
+    on_rows(chunk_len(c), [&](uint64_t i) {
+      memcpy(files[c * m + i] + payload_bytes, h_tag[b] + i * PIR_MAC_BYTES, PIR_MAC_BYTES);
+    });
+    return PIR_OK;
+  };
+  for (uint64_t c = 0; c < nchunks && !rc; ++c) {
+    const int b = (int)(c & 1);
+    const uint64_t n = chunk_len(c);
+    if (c >= 2 && (rc = scatter(c - 2))) break;
+    on_rows(n, [&](uint64_t i) {
+      memcpy(h_pay[b] + i * payload_bytes, files[c * m + i], payload_bytes);
+    });
+    if (hipMemcpyAsync(d_pay[b], h_pay[b], (size_t)n * payload_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        pir::launch_hmac_sha256_files(d_pay[b], payload_bytes, n, payload_bytes, st, d_tag[b],
+                                      PIR_MAC_BYTES, s) != hipSuccess ||
+        hipMemcpyAsync(h_tag[b], d_tag[b], (size_t)n * PIR_MAC_BYTES, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipEventRecord(done[b], s) != hipSuccess)
+      rc = PIR_EHIP;
+  }
+  for (uint64_t c = nchunks >= 2 ? nchunks - 2 : 0; c < nchunks && !rc; ++c) rc = scatter(c);
+  if (s) (void)hipStreamSynchronize(s);
+  for (int i = 0; i < 2; ++i) {
+    if (h_pay[i]) (void)hipHostFree(h_pay[i]);
+    if (h_tag[i]) (void)hipHostFree(h_tag[i]);
+    if (d_pay[i]) (void)hipFree(d_pay[i]);
+    if (d_tag[i]) (void)hipFree(d_tag[i]);
+    if (done[i]) (void)hipEventDestroy(done[i]);
+  }
+  if (s) (void)hipStreamDestroy(s);
+  return rc;
+}
+
+int pir_mac_check(const uint8_t* record, uint32_t payload_bytes, const uint8_t key[16]) {
+  if (!record || !key || payload_bytes == 0) return PIR_EINVAL;
+  uint8_t tag[PIR_MAC_BYTES];
+  pir::hmac_sha256_host(pir::hmac_states(key), record, payload_bytes, tag);
+  uint32_t diff = 0;
+  for (int i = 0; i < PIR_MAC_BYTES; ++i) diff |= (uint32_t)(tag[i] ^ record[payload_bytes + i]);
+  return diff ? 1 : 0;
 }
 
 }  // extern "C"

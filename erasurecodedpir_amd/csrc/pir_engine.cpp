@@ -22,9 +22,11 @@
 #include <string>
 #include <vector>
 
+#include "../../include/pir_client.h"
 #include "../../include/pir_engine.h"
 #include "pir_coefs.h"
 #include "pir_kernels.h"
+#include "pir_mac.h"
 #include "pir_mp.h"
 #include "pir_shamir.h"
 #include "pir_woodruff.h"
@@ -2017,8 +2019,9 @@ int pir_engine_fill_shard_random(pir_engine_t* e, uint64_t seed) {
   return PIR_OK;
 }
 
-int pir_engine_encode_across_dev(pir_engine_t* e, const uint8_t* d_files, uint64_t file_pitch,
-                                 uint64_t num_files, int k) {
+// pir_engine_encode_across_dev; with `key` the synthetic CheckMAC database (d_files == nullptr)
+static int encode_across_dev(pir_engine_t* e, const uint8_t* d_files, uint64_t file_pitch,
+                             uint64_t num_files, int k, const uint8_t* key) {
   if (!e) return fail(PIR_EINVAL, "null engine");
   if (k < 1 || k > 16) return fail(PIR_EINVAL, "k = %d outside [1,16]", k);
   if (d_files && file_pitch < e->cfg.record_bytes) return fail(PIR_EINVAL, "file_pitch < record_bytes");
@@ -2029,11 +2032,46 @@ int pir_engine_encode_across_dev(pir_engine_t* e, const uint8_t* d_files, uint64
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
   const uint64_t row0 = (uint64_t)e->cfg.partition_index * e->rows;
-  HIP_TRY(pir::launch_encode_across(d_files, file_pitch, num_files, k, e->cfg.party_index,
-                                    e->d_shard, e->rows, row0, e->pitch, e->cfg.record_bytes,
-                                    e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return PIR_OK;
+  // CheckMAC: the 257 distinct synthetic payloads (bytes v, and file 1's ramp as entry 256) are
+  // materialised once, tagged by k_hmac_sha256_files, and the encode reads the 257 x 32 table
+  uint8_t *d_pay = nullptr, *d_tags = nullptr;
+  const uint32_t payload = key ? e->cfg.record_bytes - PIR_MAC_BYTES : 0;
+  int rc = PIR_OK;
+  if (key) {
+    std::vector<uint8_t> pay((size_t)257 * payload);
+    for (uint32_t v = 0; v < 256; ++v) memset(&pay[(size_t)v * payload], (int)v, payload);
+    for (uint32_t j = 0; j < payload; ++j) pay[(size_t)256 * payload + j] = (uint8_t)j;
+    if (hipMalloc(&d_pay, pay.size()) != hipSuccess ||
+        hipMalloc(&d_tags, 257 * PIR_MAC_BYTES) != hipSuccess)
+      rc = fail(PIR_ENOMEM, "tag table");
+    else if (hipMemcpyAsync(d_pay, pay.data(), pay.size(), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+             hipStreamSynchronize(e->stream) != hipSuccess ||  // pay is pageable and dies here
+             pir::launch_hmac_sha256_files(d_pay, payload, 257, payload, pir::hmac_states(key),
+                                           d_tags, PIR_MAC_BYTES, e->stream) != hipSuccess)
+      rc = fail(PIR_EHIP, "tag table");
+  }
+  if (!rc && (pir::launch_encode_across(d_files, file_pitch, num_files, k, e->cfg.party_index,
+                                        e->d_shard, e->rows, row0, e->pitch, e->cfg.record_bytes,
+                                        e->stream, d_tags, payload) != hipSuccess ||
+              hipStreamSynchronize(e->stream) != hipSuccess))
+    rc = fail(PIR_EHIP, "encode_across: %s", hipGetErrorString(hipGetLastError()));
+  if (d_pay) (void)hipFree(d_pay);
+  if (d_tags) (void)hipFree(d_tags);
+  return rc;
+}
+
+int pir_engine_encode_across_dev(pir_engine_t* e, const uint8_t* d_files, uint64_t file_pitch,
+                                 uint64_t num_files, int k) {
+  return encode_across_dev(e, d_files, file_pitch, num_files, k, nullptr);
+}
+
+int pir_engine_encode_across_synthetic_mac(pir_engine_t* e, uint64_t num_files, int k,
+                                           const uint8_t key[16]) {
+  if (!e || !key) return fail(PIR_EINVAL, "null argument");
+  if (e->cfg.record_bytes <= PIR_MAC_BYTES)
+    return fail(PIR_EINVAL, "record_bytes %u leaves no payload before the %d-byte tag",
+                e->cfg.record_bytes, PIR_MAC_BYTES);
+  return encode_across_dev(e, nullptr, 0, num_files, k, key);
 }
 
 int pir_engine_encode_across_rows(pir_engine_t* e, const uint8_t* const* files, uint64_t num_files,
@@ -2915,6 +2953,15 @@ int pir_engine_set_party_index(pir_engine_t* e, int party_index) {
   std::lock_guard<std::mutex> lk(e->mu);
   e->cfg.party_index = party_index;  // read at enqueue time (a kernel argument), not by kernels
   return PIR_OK;                     // already queued
+}
+
+int pir_engine_fill_random_dev(pir_engine_t* e, void* d_dst, size_t bytes, uint64_t seed) {
+  if (!e || (!d_dst && bytes)) return fail(PIR_EINVAL, "null argument");
+  if (!bytes) return PIR_OK;
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(pir::launch_fill_random(static_cast<uint8_t*>(d_dst), bytes, seed, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return PIR_OK;
 }
 
 int pir_engine_memcpy_h2d(pir_engine_t* e, void* d_dst, const void* h_src, size_t bytes) {

@@ -2914,7 +2914,9 @@ __global__ void k_fill_shard(uint8_t* __restrict__ shard, uint64_t rows, uint32_
 // gf_pow(q, j) * file[src] over GF(2^8)/0x11d.  One lane per 16-byte chunk of a row; the k
 // coefficients are wave-uniform (scalar branches over their bits, x * alpha^b by xtime).
 // files == nullptr: the reference's synthetic database (client.cpp:16-33): file v holds the
-// byte (v & 0xff) in every position, file 1 holds 0, 1, 2, ....
+// byte (v & 0xff) in every position, file 1 holds 0, 1, 2, ....  With `tags` (CheckMAC) those
+// are the payloads, `payload` bytes long, and bytes [payload, payload + 32) of file v come from
+// the 257-entry table of their HMAC tags: entry (v & 0xff), entry 256 for file 1.
 // ------------------------------------------------------------------------------------------
 struct EncodeCoefs {
   uint8_t c[16];
@@ -2938,10 +2940,24 @@ __device__ __forceinline__ uint32_t synth_word(uint64_t v, uint32_t b0) {  // by
   return (uint32_t)(v & 0xff) * 0x01010101u;
 }
 
+// synth_word with the bytes at or past `payload` replaced by file v's tag
+__device__ __forceinline__ uint32_t synth_word_mac(uint64_t v, uint32_t b0, uint32_t payload,
+                                                   const uint8_t* __restrict__ tags) {
+  uint32_t w = synth_word(v, b0);
+  if (b0 + 4 <= payload) return w;
+  const uint8_t* tag = tags + (v == 1 ? 256u : (uint32_t)(v & 0xff)) * 32u;
+  for (int t = 0; t < 4; ++t) {
+    const uint32_t o = b0 + t - payload;  // wraps below payload: fails the test
+    if (o < 32u) w = (w & ~(0xffu << (8 * t))) | ((uint32_t)tag[o] << (8 * t));
+  }
+  return w;
+}
+
 __global__ void k_encode_across(const uint8_t* __restrict__ files, uint64_t fpitch,
                                 uint64_t nfiles, uint64_t encdb, int k, EncodeCoefs co,
                                 uint8_t* __restrict__ shard, uint64_t rows, uint64_t row0,
-                                uint32_t pitch, uint32_t efs) {
+                                uint32_t pitch, uint32_t efs,
+                                const uint8_t* __restrict__ tags, uint32_t payload) {
   const uint32_t cpr = pitch / 16;
   for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < rows * cpr;
        idx += (uint64_t)gridDim.x * blockDim.x) {
@@ -2967,6 +2983,11 @@ __global__ void k_encode_across(const uint8_t* __restrict__ files, uint64_t fpit
           w[t] = v;
         }
         x = make_uint4(w[0], w[1], w[2], w[3]);
+      } else if (tags) {
+        x = make_uint4(synth_word_mac(src, ch * 16u, payload, tags),
+                       synth_word_mac(src, ch * 16u + 4, payload, tags),
+                       synth_word_mac(src, ch * 16u + 8, payload, tags),
+                       synth_word_mac(src, ch * 16u + 12, payload, tags));
       } else {
         x = make_uint4(synth_word(src, ch * 16u), synth_word(src, ch * 16u + 4),
                        synth_word(src, ch * 16u + 8), synth_word(src, ch * 16u + 12));
@@ -3546,7 +3567,8 @@ hipError_t launch_fill_random(uint8_t* d, size_t bytes, uint64_t seed, hipStream
 
 hipError_t launch_encode_across(const uint8_t* d_files, uint64_t file_pitch, uint64_t nfiles,
                                int k, int party, uint8_t* d_shard, uint64_t rows, uint64_t row0,
-                               uint32_t pitch, uint32_t efs, hipStream_t s) {
+                               uint32_t pitch, uint32_t efs, hipStream_t s,
+                               const uint8_t* d_tags, uint32_t payload) {
   if (k < 1 || k > 16) return hipErrorInvalidValue;
   EncodeCoefs co{};
   for (int j = 0; j < k; ++j) {  // gf_pow(party, j) (coding.cpp:46-60; pow(0, e) == 1)
@@ -3565,7 +3587,8 @@ hipError_t launch_encode_across(const uint8_t* d_files, uint64_t file_pitch, uin
   const uint64_t encdb = (nfiles + k - 1) / k;
   const uint64_t total = rows * (pitch / 16);
   hipLaunchKernelGGL(k_encode_across, dim3(grid_1d(total)), dim3(256), 0, s,
-                     d_files, file_pitch, nfiles, encdb, k, co, d_shard, rows, row0, pitch, efs);
+                     d_files, file_pitch, nfiles, encdb, k, co, d_shard, rows, row0, pitch, efs,
+                     d_tags, payload);
   return hipGetLastError();
 }
 

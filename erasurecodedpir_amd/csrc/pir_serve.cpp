@@ -286,7 +286,11 @@ std::string setup(const MVal& req) {  // server.go:295-331
            "Woodruff (5) modes are served by this engine";
   if (mode == 5 && (k != 1 || b != 0 || t < 1)) return "Woodruff mode needs K = 1, B = 0 and T >= 1";
   if (mode == 5 && log_files > 31) return "Woodruff mode serves at most 2^31 records";
-  if (mac != 0) return "CheckMAC setups are outside this engine's scope";
+  if (mac != 0 && mac != 1) return "CheckMAC is 0 or 1";
+  if (mac && (mode == 2 || mode == 3 || mode == 5))
+    return "CheckMAC setups of the Shamir, Hollanti and Woodruff modes are outside this engine's scope";
+  // server.go:303-304: a CheckMAC request's FileSizeBytes counts the tag
+  if (mac && fsz <= MAC_SIZE_BYTES) return "a CheckMAC setup needs FileSizeBytes > 32 (payload + tag)";
   if (mode == 0 && (t != 1 || b != 0)) return "tree mode needs T = 1 and B = 0";
   if (mode == 1 && t < 1) return "multiparty mode needs T >= 1";
   if (log_files < 0 || log_files > 40 || fsz < 1 || k < 1 || k > 16 || r < 0 || rho < 1 || b < 0)
@@ -299,7 +303,7 @@ std::string setup(const MVal& req) {  // server.go:295-331
   g.key_len = 0;
   g.mode = -1;
   if (mode == 5) WOODRUFF_DERIVATIVE = 0;  // the value mode only, like the Go server
-  setSystemParams(log_files, fsz, t, k, r, b, rho, mac, mode);
+  setSystemParams(log_files, mac ? fsz - MAC_SIZE_BYTES : fsz, t, k, r, b, rho, mac, mode);
   if (g.party > NUM_PARTIES) return "this server's party index exceeds NUM_PARTIES";
   const int rounds = mode == 1 ? NUM_RSS_KEYS : (mode == 4 ? NUM_CD_KEYS : NUM_ROUNDS);
   if (rounds < 1 || rounds > PIR_MAX_ROUNDS)
@@ -322,7 +326,10 @@ std::string setup(const MVal& req) {  // server.go:295-331
   if (pir_engine_create(&c, &g.eng) != PIR_OK) return std::string("engine: ") + pir_engine_last_error();
   if (ENCODE_ACROSS) {
     // the synthetic database of client.cpp:16-33, encoded across files on the GPU
-    if (pir_engine_encode_across_dev(g.eng, nullptr, 0, (uint64_t)NUM_FILES, K) != PIR_OK)
+    // (under CheckMAC with each file's tag behind its payload, client.cpp:29-31)
+    static const uint8_t kMacKey[] = "1234567812345678";  // client.cpp:19
+    if ((mac ? pir_engine_encode_across_synthetic_mac(g.eng, (uint64_t)NUM_FILES, K, kMacKey)
+             : pir_engine_encode_across_dev(g.eng, nullptr, 0, (uint64_t)NUM_FILES, K)) != PIR_OK)
       return std::string("encode: ") + pir_engine_last_error();
   } else {
     // the synthetic database of client.cpp:16-33, encoded within files (client.cpp:99-103) on

@@ -624,6 +624,8 @@ namespace pir_shim {
 HermiteEncodeFn g_encode_hermite = nullptr;
 const WoodruffHooks* g_woodruff = nullptr;
 
+int device() { return device_default(); }
+
 void with_engine(server* s, int nq, const std::function<void(pir_engine_t*)>& fn) {
   ShimState* st = state_of(s);
   std::lock_guard<std::mutex> lk(st->mu);
@@ -850,7 +852,8 @@ void setSystemParams(int logNumFiles, int fileSizeBytes, int t, int k, int r, in
     abort();
   }
   if ((mode == 2 || mode == 3 || mode == 5) && checkMac) {
-    fprintf(stderr, "pir shim: CheckMAC setups are outside the engine's scope\n");
+    fprintf(stderr, "pir shim: CheckMAC setups of the encode-within modes (2, 3, 5) are outside "
+            "the engine's scope (modes 0, 1 and 4 are served)\n");
     abort();
   }
   RHO = rho; K = k; T = t; R = r; B = b;
@@ -1333,16 +1336,15 @@ void runWoodruffQueryThread(server* s, uint8_t* key, int threadNum, int startInd
   pir_shim::g_woodruff->run_thread(s, key, threadNum, startIndex, endIndex, result);
 }
 
-// client.cpp:16-33 (synthetic DB; MAC tags are outside this engine's scope).  The files share
+// client.cpp:16-33 (synthetic DB).  Under CHECK_MAC every file carries HMAC-SHA256(macKey,
+// payload) at [PAYLOAD_SIZE_BYTES, +32) (client.cpp:29-31): the payloads take 257 values (the
+// byte i & 0xff, and file 1's ramp), so 257 tags are computed here with mac() and the fill
+// threads copy them; pirClientTagFiles retags a caller's own database on the GPU.  The files share
 // one allocation (held in c->ctx, which the reference uses for an unused EVP context) and are
 // filled by host threads: the reference's per-file malloc + memset of NUM_FILES rows is most of
 // a large setup's host time (2^26 x 1 KiB for configs[4]'s k = 5).
 void initialize_client(client* c, uint8_t log_num_files, uint32_t file_size_bytes) {
   (void)file_size_bytes;
-  if (CHECK_MAC) {
-    fprintf(stderr, "pir shim: CHECK_MAC setups are outside the engine's scope\n");
-    abort();
-  }
   c->macCtx = nullptr;
   c->macKey = (uint8_t*)"1234567812345678";
   const uint64_t n = 1ull << log_num_files, fb = FILE_SIZE_BYTES;
@@ -1355,6 +1357,16 @@ void initialize_client(client* c, uint8_t log_num_files, uint32_t file_size_byte
   }
   c->ctx = block;
   const uint32_t pb = PAYLOAD_SIZE_BYTES;
+  std::vector<uint8_t> tags;  // entry v: the tag of the payload of bytes v; entry 256: the ramp's
+  if (CHECK_MAC && fb >= (uint64_t)pb + MAC_SIZE_BYTES) {
+    tags.resize((size_t)257 * MAC_SIZE_BYTES);
+    std::vector<uint8_t> pay(pb);
+    for (int v = 0; v <= 256; ++v) {
+      for (uint32_t j = 0; j < pb; ++j) pay[j] = (uint8_t)(v == 256 ? j : (uint32_t)v);
+      mac(c->macKey, pay.data(), (int)pb, tags.data() + (size_t)v * MAC_SIZE_BYTES, MAC_SIZE_BYTES);
+    }
+  }
+  const uint8_t* tagtab = tags.empty() ? nullptr : tags.data();
   const int T = shim_threads();
   std::vector<std::thread> th;
   for (int t = 0; t < T; ++t)
@@ -1366,6 +1378,9 @@ void initialize_client(client* c, uint8_t log_num_files, uint32_t file_size_byte
         if (fb > pb) memset(f + pb, 0, fb - pb);
         if (i == 1)
           for (uint32_t j = 0; j < pb; ++j) f[j] = (uint8_t)j;
+        if (tagtab)
+          memcpy(f + pb, tagtab + (size_t)(i == 1 ? 256 : (i & 0xff)) * MAC_SIZE_BYTES,
+                 (size_t)MAC_SIZE_BYTES);
       }
     });
   for (auto& x : th) x.join();

@@ -19,6 +19,8 @@ namespace pir_shim {
 void with_engine(server* s, int nq, const std::function<void(pir_engine_t*)>& fn);
 // "pir engine failure in <what>: <last error>" and abort (the reference's handleErrors())
 [[noreturn]] void engine_failure(const char* what);
+// the device the shim's engines and client helpers use (pirSetDevice, $PIR_DEVICE or 0)
+int device();
 
 // The Hermite half of encode_within_files_server's GPU setup: pir_engine_encode_hermite_rows,
 // registered by pir_server_shamir.cpp when it is linked (nullptr otherwise: the setup refuses).

@@ -96,6 +96,17 @@ class Engine:
             if d_f is not None:
                 self.free_dev(d_f)
 
+    def encode_across_synthetic_mac(self, num_files, k, key):
+        """encode_across(num_files, k) for a CheckMAC setup: the synthetic files are
+        record_bytes - 32 payload bytes followed by their HMAC-SHA256 tag under the 16-byte
+        `key` (client.cpp:29-31), the tags computed on the GPU."""
+        key = np.frombuffer(bytes(key), np.uint8).copy()
+        if key.size != 16:
+            raise ValueError("the tag key is 16 bytes")
+        check(self._lib.pir_engine_encode_across_synthetic_mac(
+            self._h, num_files, k, key.ctypes.data_as(ctypes.c_void_p)),
+            "encode_across_synthetic_mac")
+
     def encode_within(self, num_files, file_bytes, k, files=None, party=0):
         """The Hollanti-mode shard (encoded within files) computed on the GPU (client.cpp:43-56,
         99-103): from `files` (num_files x file_bytes host array) or, files=None, the
@@ -482,6 +493,11 @@ class Engine:
         (server.partyIndex, src/c/server.h:16)."""
         check(self._lib.pir_engine_set_party_index(self._h, int(party_index)), "set_party_index")
         self.party_index = int(party_index)
+
+    def fill_random_dev(self, d_ptr, nbytes, seed):
+        """nbytes pseudo-random bytes from the engine's generator into device memory."""
+        check(self._lib.pir_engine_fill_random_dev(self._h, d_ptr, nbytes, seed),
+              "fill_random_dev")
 
     def h2d(self, d_ptr, host):
         h, hp = _buf(host)

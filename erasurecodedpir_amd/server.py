@@ -323,6 +323,17 @@ class Client:
         NUM_ENCODED_FILES) coefficient vectors."""
         return generateHollantiQuery(index, self.c)
 
+    def tag_files(self):
+        """pirClientTagFiles: after the caller wrote their own payloads into the files of a
+        CheckMAC setup, every file's tag recomputed on the GPU."""
+        self._lib.pirClientTagFiles(ctypes.byref(self.c))
+
+    def file(self, i):
+        """File i (FILE_SIZE_BYTES bytes: the payload and, under CheckMAC, its tag)."""
+        if not 0 <= i < _lib.global_int("NUM_FILES"):
+            raise IndexError(i)
+        return ctypes.string_at(self.c.unencoded_files[i], _lib.global_int("FILE_SIZE_BYTES"))
+
     def free_client(self):
         if self.c.unencoded_files:
             self._lib.free_client(ctypes.byref(self.c))

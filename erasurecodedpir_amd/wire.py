@@ -71,13 +71,14 @@ class Conn:
 
 
 def setup(addr, log_num_files, file_size_bytes, k, r, rho=1, num_threads=1, is_byzantine=0,
-          mode=0, t=1, b=0):
-    """SETUP_REQUEST with the fields of common.go:51-65 (no MAC): mode 0 tree, 1 multiparty,
-    2 Shamir, 3 Hollanti, 4 covering design, 5 Woodruff (k = 1)."""
+          mode=0, t=1, b=0, check_mac=0):
+    """SETUP_REQUEST with the fields of common.go:51-65: mode 0 tree, 1 multiparty, 2 Shamir,
+    3 Hollanti, 4 covering design, 5 Woodruff (k = 1).  check_mac = 1 (modes 0, 1, 4): every
+    record ends in its 32-byte HMAC-SHA256 tag and file_size_bytes counts it (server.go:303)."""
     host, port = addr
     req = {"BenchmarkDir": "", "LogNumFiles": log_num_files, "FileSizeBytes": file_size_bytes,
            "T": t, "K": k, "R": r, "B": b, "Rho": rho, "Mode": mode, "IsByzantine": is_byzantine,
-           "DelayTime": 0, "NumThreads": num_threads, "CheckMAC": 0}
+           "DelayTime": 0, "NumThreads": num_threads, "CheckMAC": int(check_mac)}
     with Conn(host, port) as c:
         return c.call(SETUP_REQUEST, req)
 
@@ -127,13 +128,17 @@ def woodruff_query(addr, key):
         return c.call(WOODRUFF_SEARCH_REQUEST, {"Key": bytes(np.asarray(key, np.uint8))})
 
 
-def tree_query(addrs, index, log_num_files, file_size_bytes, k, r, rho=1, device=0):
+def tree_query(addrs, index, log_num_files, file_size_bytes, k, r, rho=1, device=0, check_mac=0):
     """src/client/tree.go:17-175 for one record: returns (record bytes, per-server responses,
     erasure list).  Needs the sizing globals of setSystemParams (set here) and a GPU for key
-    generation (pir_client.h)."""
+    generation (pir_client.h).  check_mac: file_size_bytes counts the 32-byte tag, as in setup();
+    the record returned is payload + tag (client.mac_check verifies it)."""
     from . import client as C
     from . import server as S
-    S.setSystemParams(log_num_files, file_size_bytes, 1, k, r, 0, rho, 0, 0)
+    if check_mac:
+        S.setSystemParams(log_num_files, file_size_bytes - C.MAC_BYTES, 1, k, r, 0, rho, 1, 0)
+    else:
+        S.setSystemParams(log_num_files, file_size_bytes, 1, k, r, 0, rho, 0, 0)
     prm = S.params()
     p, n, nq, R = prm["NUM_PARTIES"], prm["LOG_NUM_ENCODED_FILES"], prm["NUM_ROUNDS"], prm["R"]
     if len(addrs) != p:

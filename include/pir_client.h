@@ -5,6 +5,8 @@
  *   pir_gen_keys       genOptimizedDPF          dpf_tree.cpp:142-274 (root seeds supplied by the
  *                                               caller; the reference draws them with RAND_bytes)
  *   pir_final_cw       generate_opt_DPF_tree_query's finalCW values   client.cpp:144-153
+ *   pir_mac_files_*    the CheckMAC record tags of initialize_client  client.cpp:29-31
+ *   pir_mac_check      the client's check of a decoded record         benchmark.go:190-207
  */
 #ifndef PIR_CLIENT_H
 #define PIR_CLIENT_H
@@ -21,6 +23,25 @@ int pir_gen_keys(int device, int n, uint64_t index, const uint8_t *fcw, int p, i
                  const uint8_t *root_seeds, uint8_t *keys_out);
 /* out[a*(p-1) + j-2] = gf_pow(j, rho*(a+1)) ^ 1 for j = 2..p, a < nq (GF(2^8)/0x11d) */
 void pir_final_cw(int p, int nq, int rho, uint8_t *out);
+
+/* ---- record tags: HMAC-SHA256 under a 16-byte key (utils.cpp:32-34), computed on the GPU ---- */
+#define PIR_MAC_BYTES 32
+/* tag of row i (d_files + i*file_pitch, payload_bytes bytes) -> d_tags + i*tag_pitch, 32 bytes.
+ * In place with d_tags = d_files + payload_bytes, tag_pitch = file_pitch (only [0, payload_bytes)
+ * of a row is read).  Any alignment.  Asynchronous on `stream` (a hipStream_t of `device`, or
+ * NULL).  num_files == 0 touches nothing; null pointers, payload_bytes == 0,
+ * file_pitch < payload_bytes and tag_pitch < 32 are PIR_EINVAL. */
+int pir_mac_files_dev(int device, const uint8_t *d_files, uint64_t file_pitch, uint64_t num_files,
+                      uint32_t payload_bytes, const uint8_t key[16],
+                      uint8_t *d_tags, uint64_t tag_pitch, void *stream);
+/* host rows (client.unencoded_files): payloads staged through two pinned buffers in chunks of
+ * ~64 MiB ($PIR_MAC_CHUNK_FILES, read per call: the chunk in files), tagged on the GPU, only the
+ * tags copied back to files[i] + payload_bytes.  Synchronous. */
+int pir_mac_files_rows(int device, uint8_t *const *files, uint64_t num_files,
+                       uint32_t payload_bytes, const uint8_t key[16]);
+/* host only, no GPU: 0 if record[payload_bytes, +32) is the tag of record[0, payload_bytes),
+ * 1 if not, a negative PIR_E* code for bad arguments; the comparison does not exit early */
+int pir_mac_check(const uint8_t *record, uint32_t payload_bytes, const uint8_t key[16]);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,13 @@ int pir_engine_fill_shard_random(pir_engine_t *e, uint64_t seed);
  * reference's synthetic database (client.cpp:16-33). */
 int pir_engine_encode_across_dev(pir_engine_t *e, const uint8_t *d_files, uint64_t file_pitch,
                                  uint64_t num_files, int k);
+/* pir_engine_encode_across_dev(e, NULL, 0, num_files, k) for a CheckMAC setup: the synthetic
+ * files are record_bytes - 32 payload bytes followed by HMAC-SHA256(key[16], payload)
+ * (client.cpp:29-31).  The payloads take 257 values, so 257 tags are computed on the GPU
+ * (pir_mac_files_dev's kernel) and the encode reads them from that table.  record_bytes < 33 is
+ * PIR_EINVAL. */
+int pir_engine_encode_across_synthetic_mac(pir_engine_t *e, uint64_t num_files, int k,
+                                           const uint8_t key[16]);
 /* pir_engine_encode_across_dev from the client's HOST file rows (client.unencoded_files:
  * num_files row pointers, record_bytes read from each): the server setup of server.go:299-331
  * with the encode on the GPU.  Per ~64 MiB chunk of this engine's rows, host threads gather the
@@ -374,6 +381,9 @@ int pir_engine_sync(pir_engine_t *e);
 int pir_engine_alloc_dev(pir_engine_t *e, size_t bytes, void **d_ptr);
 /* release a pir_engine_alloc_dev buffer before the engine is destroyed (waits for the device) */
 int pir_engine_free_dev(pir_engine_t *e, void *d_ptr);
+/* `bytes` pseudo-random bytes, a function of (seed, position), written to d_dst by the engine's
+ * generator on its stream (benchmarks: a device-resident database without a host copy) */
+int pir_engine_fill_random_dev(pir_engine_t *e, void *d_dst, size_t bytes, uint64_t seed);
 int pir_engine_memcpy_h2d(pir_engine_t *e, void *d_dst, const void *h_src, size_t bytes);
 int pir_engine_memcpy_d2h(pir_engine_t *e, void *h_dst, const void *d_src, size_t bytes);
 

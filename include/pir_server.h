@@ -287,6 +287,12 @@ void pirRunTreeQueryThreads(server *s, uint8_t *key, int numThreads, uint8_t **r
 
 /* Engine device used by servers created after this call (default: $PIR_DEVICE or 0). */
 void pirSetDevice(int device);
+/* CheckMAC setups (setSystemParams checkMac = 1; modes 0, 1 and 4): initialize_client tags its
+ * synthetic files itself.  A caller who then writes their own payloads into
+ * c->unencoded_files[i][0, PAYLOAD_SIZE_BYTES) calls this before the encode: every file's tag at
+ * [PAYLOAD_SIZE_BYTES, +32) is recomputed under c->macKey on the GPU (pir_mac_files_rows).
+ * Aborts if CHECK_MAC is 0. */
+void pirClientTagFiles(client *c);
 /* indexList rows were written by something other than encode_across_files_server: the next
  * query re-uploads the shard to HBM (encode_across_files_server does this implicitly).  After a
  * GPU setup, call pirServerSyncRows BEFORE writing the rows directly. */
