@@ -1,5 +1,5 @@
 // pir_bits.h -- bit-matrix transposes of the transposed four-Russians scan (pir_scan_t.hip).
-// Plain integer code, host and device (tools/test_bits.cpp checks it on the CPU).
+// Plain integer code, host and device (tests/test_bits_nibble.py checks it on the CPU).
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +19,14 @@ PIR_HD void bit_swap(uint32_t& a, uint32_t& b, uint32_t m) {
   const uint32_t t = ((a >> S) ^ b) & m;
   b ^= t;
   a ^= t << S;
+}
+
+// 4 rows x 32 bits -> 32 nibbles: afterwards nibble i of x[k] holds bit (4i + k) of the original
+// rows, row r in bit r (eight independent 4 x 4 transposes, one per nibble column: the 2-bit and
+// 1-bit stages of transpose8x32)
+PIR_HD void transpose4x32(uint32_t (&x)[4]) {
+  bit_swap<2>(x[0], x[2], 0x33333333u); bit_swap<2>(x[1], x[3], 0x33333333u);
+  bit_swap<1>(x[0], x[1], 0x55555555u); bit_swap<1>(x[2], x[3], 0x55555555u);
 }
 
 // 8 rows x 32 bits -> 32 bytes: afterwards byte i of x[k] holds bit (8i + k) of the original

@@ -8,14 +8,19 @@
 // combination by GPR index (pir_m4r.h): one index switch per plane per 4 rows, whose cost grows
 // with the number of planes (2.2 TB/s at 64 planes, 3.4 at 40: profiles/r02_micro/).
 //
-// Here the roles are swapped.  Per lane and 8 rows, bit j of the lane's 8 row dwords forms an
-// 8-bit index n_j (an 8 x 32 bit transpose of the rows, pir_bits.h), and the wave keeps in LDS a
-// table of the 256 XOR combinations of the 8 rows' coefficient words, T[v] = XOR_{r: bit r of v}
-// w_r.  Then for every bit position j: Zt[j] ^= T[n_j] -- one ds_read_b64 and two v_xor --
-// where Zt[j] (64 bits) is bit j of the lane's dword in every plane at once.  The cost per row
-// no longer depends on the number of planes (up to 64), and no scalar index setting is left in
-// the loop.  At the end Zt is transposed back to planes (32 x 32 bit transposes) and folded by
-// the alpha powers as in k_scan_uni; slabs and k_reduce are unchanged.
+// Here the roles are swapped: the index comes from the shard's bits, the table from the
+// coefficients.  For every 4 consecutive rows of a wave's 64-row chunk the wave keeps in LDS the
+// 16 XOR combinations of the rows' coefficient words, T_t[v] = XOR_{r: bit r of v} w_{4t+r}: 16
+// tables per chunk, each aligned to its own size (128 B of 8-byte entries), so that every entry
+// has banks of its own and any set of indices reads without a bank conflict.  Per lane and 8
+// rows, bit j of rows 0-3 and of rows 4-7 forms two 4-bit indices (4 x 32 bit transposes of the
+// rows, pir_bits.h), and for every bit position j: Zt[j] ^= T_lo[n_j] ^ T_hi[n'_j] -- two
+// ds_read_b64 and two v_bitop3 (XOR3) -- where Zt[j] (64 bits) is bit j of the lane's dword in
+// every plane at once.  The cost per row does not depend on the number of planes (up to 64), and
+// no scalar index setting is left in the loop.  At the end Zt is transposed back to planes (32 x
+// 32 bit transposes) and folded by the alpha powers as in k_scan_uni; slabs and k_reduce are
+// unchanged.  (One 256-entry table per 8 rows, the first form, spent 63 % of its LDS cycles on
+// bank conflicts and rebuilt the table every 8 rows: DESIGN.md, Transposed four-Russians scan.)
 //
 // One record per wave row at one dword per lane (pitch >= 256 B; column groups of 64 dwords
 // along grid y), NRP = 4 or 8 coefficient bytes per record (NQ <= NRP rounds), rows of a wave
@@ -42,8 +47,13 @@ void k_scan_t(const uint8_t* __restrict__ shard, uint64_t nrec, uint32_t pitch, 
   static_assert(NQ >= 1 && NQ <= NRP, "rounds");
   constexpr int WD = NRP / 4;  // coefficient words per record (rounds 0-3, 4-7)
   constexpr int GW = kColGroupLanes;
-  // per wave: T[v] at [v * WD]; read as uint2 (ds_read_b64) when WD == 2, hence 8-aligned
-  __shared__ alignas(8) uint32_t tab[kScanTWaves][256 * WD];
+  // per wave: the 16 nibble tables of a 64-row chunk, table t (rows 4t .. 4t + 3) at t * kTabBytes,
+  // its 16 entries of ESZ bytes read as uint2 (ds_read_b64) when WD == 2.  A table aligned to its
+  // own size gives every entry its own bank(s): any set of indices reads without a bank conflict
+  using Ent = typename std::conditional<WD == 2, uint2, uint32_t>::type;
+  constexpr int ESH = WD == 2 ? 3 : 2;        // log2 of the entry size
+  constexpr int kTabBytes = 16 << ESH;        // 128 or 64
+  __shared__ alignas(128) uint32_t tab[kScanTWaves][16 * kTabBytes / 4];
   __shared__ uint32_t red[NQ * GW];
   __shared__ uint32_t next_chunk;
   for (int i = threadIdx.x; i < NQ * GW; i += blockDim.x) red[i] = 0;
@@ -108,10 +118,35 @@ void k_scan_t(const uint8_t* __restrict__ shard, uint64_t nrec, uint32_t pitch, 
       }
       return cw;
     };
-    // table entries lane + 64 k: the XOR of w_r over the set bits r < 6 of the lane, then w6, w7
-    uint32_t lm[6];
+    // the chunk's 16 nibble tables, built lane-parallel: lane l holds row l's words, table l >> 2
+    // covers the lane's own quad of rows, and the lane writes its entries 4 (l & 3) .. + 3 (row
+    // bits 2-3 = l & 3 fixed, row bits 0-1 counting): 16 or 32 contiguous bytes.  Rows past the
+    // wave's last have zero words, so a ragged chunk needs nothing of its own
+    const uint32_t q2 = (lane & 1u) ? 0xffffffffu : 0u, q3 = (lane & 2u) ? 0xffffffffu : 0u;
+    auto build_tables = [&](const uint2& cw) __attribute__((always_inline)) {
+      uint32_t e[4][WD];
 #pragma unroll
-    for (int r = 0; r < 6; ++r) lm[r] = ((lane >> r) & 1u) ? 0xffffffffu : 0u;
+      for (int d = 0; d < WD; ++d) {
+        const int s = (int)(d ? cw.y : cw.x);
+        const uint32_t w0 = (uint32_t)__builtin_amdgcn_update_dpp(0, s, 0x00, 0xf, 0xf, false);
+        const uint32_t w1 = (uint32_t)__builtin_amdgcn_update_dpp(0, s, 0x55, 0xf, 0xf, false);
+        const uint32_t w2 = (uint32_t)__builtin_amdgcn_update_dpp(0, s, 0xaa, 0xf, 0xf, false);
+        const uint32_t w3 = (uint32_t)__builtin_amdgcn_update_dpp(0, s, 0xff, 0xf, 0xf, false);
+        e[0][d] = (w2 & q2) ^ (w3 & q3);
+        e[1][d] = e[0][d] ^ w0;
+        e[2][d] = e[0][d] ^ w1;
+        e[3][d] = e[1][d] ^ w1;
+      }
+      __builtin_amdgcn_wave_barrier();  // the previous chunk's reads are issued (LDS keeps its order)
+      uint4* const dst = reinterpret_cast<uint4*>(tw) + lane * WD;
+      if constexpr (WD == 2) {
+        dst[0] = make_uint4(e[0][0], e[0][1], e[1][0], e[1][1]);
+        dst[1] = make_uint4(e[2][0], e[2][1], e[3][0], e[3][1]);
+      } else {
+        dst[0] = make_uint4(e[0][0], e[1][0], e[2][0], e[3][0]);
+      }
+      __builtin_amdgcn_wave_barrier();  // the wave's own tables: no workgroup barrier
+    };
 
     // chunk claims (dyn): rb walks the claimed chunks' first rows; the rows and coefficient words
     // loaded ahead come from the next claimed chunk past the current one's end
@@ -136,51 +171,50 @@ void k_scan_t(const uint8_t* __restrict__ shard, uint64_t nrec, uint32_t pitch, 
       const uint32_t rb = cur * 64;
       const uint2 cwn = nxt < nch ? coefs64(nxt * 64) : make_uint2(0, 0);  // next chunk's words, in flight
       const uint32_t nb = nrows - rb < 64 ? nrows - rb : 64;
+      build_tables(cw);
       for (uint32_t j0 = 0; j0 < nb; j0 += 16) {
+        const char* const tj = reinterpret_cast<const char*>(tw) + j0 / 4 * kTabBytes;  // rows j0 ..
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
           const uint32_t j = j0 + 8 * g;
-          // ---- the wave's table of the 8 rows' coefficient combinations
-#pragma unroll
-          for (int d = 0; d < WD; ++d) {
-            uint32_t w[8];
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-              w[r] = (uint32_t)__builtin_amdgcn_readlane((int)(d ? cw.y : cw.x), (int)(j + r));
-            uint32_t e = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) e = __builtin_amdgcn_bitop3_b32(e, w[r], lm[r], 0x78);
-            const uint32_t e6 = e ^ w[6], e7 = e ^ w[7];
-            tw[lane * WD + d] = e;
-            tw[(lane + 64) * WD + d] = e6;
-            tw[(lane + 128) * WD + d] = e7;
-            tw[(lane + 192) * WD + d] = e6 ^ w[7];
-          }
-          __builtin_amdgcn_wave_barrier();  // the wave's own table: LDS keeps its order
-          // ---- bit j of the 8 rows -> index byte; one lookup per bit position
-          uint32_t (&R)[8] = *reinterpret_cast<uint32_t(*)[8]>(&x[8 * g]);  // in place
-          transpose8x32(R);
-          uint32_t id[32];
-#pragma unroll
-          for (int jj = 0; jj < 32; ++jj) id[jj] = (R[jj & 7] >> (8 * (jj >> 3))) & 0xffu;
-          // 4 chunks of 8 lookups, software-pipelined: chunk c + 1's reads are issued before
-          // chunk c's XORs (16 reads in flight; left alone the scheduler waits on each read)
-          using Ent = typename std::conditional<WD == 2, uint2, uint32_t>::type;
-          const Ent* te = reinterpret_cast<const Ent*>(tw);
+          // ---- bit jj of rows 0-3 and of rows 4-7 -> two nibble indices; two lookups per bit
+          // position.  Nibble i of L[k] / H[k] is the index of bit 4 i + k into the low / high
+          // rows' table
+          uint32_t (&L)[4] = *reinterpret_cast<uint32_t(*)[4]>(&x[8 * g]);  // in place
+          uint32_t (&H)[4] = *reinterpret_cast<uint32_t(*)[4]>(&x[8 * g + 4]);
+          transpose4x32(L);
+          transpose4x32(H);
+          // 8 steps of 4 bit positions (8 lookups), software-pipelined: step s + 1's reads are
+          // issued before step s's XORs (16 reads in flight; left alone the scheduler waits on
+          // each read).  Step s takes the even (s even) or odd nibbles of the words L[s / 2],
+          // H[s / 2] -- bit positions 8 b + 4 (s & 1) + s / 2 -- as entry byte offsets, one per
+          // byte of a pre-shifted, pre-masked copy: a lookup's address is then one byte select
+          // added to the table's.  (The copies are opaque to the compiler, which would shift and
+          // mask the word again for every lookup; made per word, they stay out of the registers.)
+          const char* const tg = tj + g * (2 * kTabBytes);
           Ent ta[8], tb[8];
-          auto issue = [&](Ent (&t)[8], int ch) __attribute__((always_inline)) {
+          auto issue = [&](Ent (&t)[8], int s) __attribute__((always_inline)) {
+            uint32_t lo = (s & 1) ? L[s >> 1] >> (4 - ESH) : L[s >> 1] << ESH;
+            uint32_t hi = (s & 1) ? H[s >> 1] >> (4 - ESH) : H[s >> 1] << ESH;
+            lo &= 0x0f0f0f0fu << ESH;
+            hi &= 0x0f0f0f0fu << ESH;
+            asm volatile("" : "+v"(lo), "+v"(hi));
 #pragma unroll
-            for (int q = 0; q < 8; ++q) t[q] = te[id[8 * ch + q]];
+            for (int b = 0; b < 4; ++b) {
+              t[2 * b] = *reinterpret_cast<const Ent*>(tg + ((lo >> (8 * b)) & 0xffu));
+              t[2 * b + 1] = *reinterpret_cast<const Ent*>(tg + kTabBytes + ((hi >> (8 * b)) & 0xffu));
+            }
             __builtin_amdgcn_sched_barrier(0);
           };
-          auto fold = [&](const Ent (&t)[8], int ch) __attribute__((always_inline)) {
+          auto fold = [&](const Ent (&t)[8], int s) __attribute__((always_inline)) {
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
+            for (int b = 0; b < 4; ++b) {
+              uint32_t (&z)[WD] = Zt[8 * b + 4 * (s & 1) + (s >> 1)];
               if constexpr (WD == 2) {
-                Zt[8 * ch + q][0] ^= t[q].x;
-                Zt[8 * ch + q][1] ^= t[q].y;
+                z[0] = __builtin_amdgcn_bitop3_b32(z[0], t[2 * b].x, t[2 * b + 1].x, 0x96);
+                z[1] = __builtin_amdgcn_bitop3_b32(z[1], t[2 * b].y, t[2 * b + 1].y, 0x96);
               } else {
-                Zt[8 * ch + q][0] ^= t[q];
+                z[0] = __builtin_amdgcn_bitop3_b32(z[0], t[2 * b], t[2 * b + 1], 0x96);
               }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -192,8 +226,15 @@ void k_scan_t(const uint8_t* __restrict__ shard, uint64_t nrec, uint32_t pitch, 
           fold(tb, 1);
           issue(tb, 3);
           fold(ta, 2);
+          issue(ta, 4);
           fold(tb, 3);
-          __builtin_amdgcn_wave_barrier();  // reads done before the next group's table
+          issue(tb, 5);
+          fold(ta, 4);
+          issue(ta, 6);
+          fold(tb, 5);
+          issue(tb, 7);
+          fold(ta, 6);
+          fold(tb, 7);
 #pragma unroll
           for (int r = 0; r < 8; ++r) x[8 * g + r] = load_rel(seq_row(j + 16 + r));
           __builtin_amdgcn_sched_barrier(0);  // one group at a time (register pressure)
