@@ -103,6 +103,9 @@ PROTOTYPES = {
     "pir_engine_shamir_response_len": (_U64, [_I, _U32]),
     "pir_engine_answer_shamir": (_I, [_P, ctypes.POINTER(_P), _U64, _U64, _P]),
     "pir_engine_answer_shamir_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
+    "pir_engine_answer_shamir_queue": (_I, [_P, ctypes.POINTER(_P), _I, _U64, _U64, _P]),
+    "pir_engine_answer_shamir_queue_dev": (_I, [_P, _P, _U64, _U64, _I, _U64, _U64, _P, _P]),
+    "pir_engine_reserve_shamir_queue": (_I, [_P, _I]),
     "pir_engine_encode_hermite_dev": (_I, [_P, _P, _U64, _U64, _U32, _I, _I]),
     "pir_engine_encode_hermite_rows": (_I, [_P, _P, _U64, _U32, _I, _I]),
     "pir_engine_woodruff_m": (_U32, [_I]),

@@ -735,6 +735,11 @@ int pir_engine_create(const pir_engine_config* cfg, pir_engine_t** out) {
     if (gs && gs[0]) e->gq_share = std::max(0, std::min(2, atoi(gs)));
     const char* gg = getenv("PIR_GQ_G");
     if (gg && gg[0]) e->gq_group = atoi(gg) >= 8 ? 8 : (atoi(gg) >= 4 ? 4 : 2);
+    // $PIR_SH_SHARE / $PIR_SH_G: queued Shamir virtual keys per shard pass (shamir_group)
+    const char* shs = getenv("PIR_SH_SHARE");
+    if (shs && shs[0]) e->sh_share = std::max(0, std::min(2, atoi(shs)));
+    const char* shg = getenv("PIR_SH_G");
+    if (shg && shg[0]) e->sh_group = atoi(shg) >= 8 ? 8 : (atoi(shg) >= 4 ? 4 : 2);
     const char* bk = getenv("PIR_BATCH_KLAST");
     if (bk) e->batch_k_last = std::max(1, std::min(12, atoi(bk)));
     const int tile = pir::fused_tile(c.num_rounds, e->pitch, e->rows, e->num_cus);

@@ -25,7 +25,9 @@ constexpr int kNumPhases = 9;
 // k_reduce; its derivative answers (fused == 7): "launch" = start -> the answer zeroed, "scan" =
 // the rows pass, the totals kernel and the columns pass, "reduce" = 0; a shared Woodruff queue
 // (fused == 8) and a shared queue of explicit-coefficient or sqrt(N) DPF keys (fused == 9):
-// answer_group_queue
+// answer_group_queue; a shared Shamir queue (fused == 10): "launch" = start -> the responses
+// zeroed, "scan" = the first key table -> the end of the last group's Hermite scan, "reduce" =
+// the last group's k_reduce + k_shamir_totals
 const char* const kQueryPhaseNames[] = {"launch", "scan", "reduce", "comm_fold", "total", "fused"};
 constexpr int kNumQueryPhases = 6;
 

@@ -45,4 +45,27 @@ hipError_t launch_shamir_totals(const ShamirDims& d, uint32_t efs, const uint8_t
                                 uint64_t key_pitch, int nq, const uint8_t* tot1, uint8_t* out,
                                 hipStream_t s);
 
+// ---- queued keys: up to kShamirSlots virtual keys per pass (pir_shamir_q.hip) ----------------
+// The rounds of the queued keys are independent virtual keys: virtual key v is round v % rounds
+// of key v / rounds, at d_keys + (v / rounds) * key_stride + (v % rounds) * key_pitch (any
+// alignment), and its response sits at out + v * resp_len.
+constexpr int kShamirSlots = 8;
+// the segmented pass takes records of at least one wave row (64 dwords)
+bool shamir_seg_takes(uint32_t pitch);
+// d_kT[j] (8-byte words, 8-byte aligned, X + Y of them): byte g = byte j of virtual key v0 + g
+// for g < ng, zero above: kyT = d_kT[0, X), kxT = d_kT[X, X + Y)
+hipError_t launch_shamir_key_table(const ShamirDims& d, const uint8_t* d_keys, uint64_t key_pitch,
+                                   uint64_t key_stride, int rounds, int v0, int ng, uint8_t* d_kT,
+                                   hipStream_t s);
+// One value pass for the table's ng slots over the records [lo, hi): strided = false gives
+// Rx[delta] (response record delta) of the deltas the range touches, strided = true Ry[gamma]
+// (record X + gamma) of the gammas it touches; out = slot 0's response, which the caller zeroed.
+hipError_t launch_shamir_seg(const ShamirDims& d, const uint8_t* vals, uint32_t pitch, uint32_t efs,
+                             const uint8_t* d_kT, int ng, uint64_t lo, uint64_t hi, bool strided,
+                             uint8_t* out, hipStream_t s);
+// d_c + 8 (i - lo): byte g = kx_g[gamma_i] * ky_g[delta_i], the share rows of an 8-round
+// explicit-coefficient scan of the Hermite rows; d_c 16-byte aligned
+hipError_t launch_shamir_coefs_g(const ShamirDims& d, const uint8_t* d_kT, uint64_t lo, uint64_t hi,
+                                 uint8_t* d_c, hipStream_t s);
+
 }  // namespace pir

@@ -278,6 +278,37 @@ class Engine:
         check(self._lib.pir_engine_answer_shamir_dev(self._h, d_keys, key_pitch, rec0, nrec,
                                                      d_result, stream), "answer_shamir_dev")
 
+    def answer_shamir_queue(self, keys, rec0=0, nrec=None):
+        """A queue of independent Shamir queries over the records [rec0, rec0 + nrec): keys is
+        (K, num_rounds, 2^x + 2^y) uint8 -> (K, num_rounds, 2^x + 2^y + 2, record_bytes), entry k
+        what answer_shamir gives for keys[k].  Where it measured faster the queued rounds share
+        passes over the shard (8 per read of it; $PIR_SH_SHARE, $PIR_SH_G: include/pir_engine.h),
+        else each key has its own answer, back to back."""
+        kl = self.shamir_key_len
+        nq = self.num_rounds
+        k = np.ascontiguousarray(np.asarray(keys, np.uint8).reshape(-1, nq, kl))
+        nk = k.shape[0]
+        nrec = self.num_rows // 2 - rec0 if nrec is None else nrec
+        ptrs = (ctypes.c_void_p * max(nk * nq, 1))(*[k[i, a].ctypes.data
+                                                     for i in range(nk) for a in range(nq)])
+        out = np.empty((nk, nq, kl + 2, self.record_bytes), np.uint8)
+        check(self._lib.pir_engine_answer_shamir_queue(self._h, ptrs, nk, rec0, nrec,
+                                                       out.ctypes.data_as(ctypes.c_void_p)),
+              "pir_engine_answer_shamir_queue")
+        return out
+
+    def answer_shamir_queue_dev(self, d_keys, key_pitch, key_stride, num_keys, rec0, nrec,
+                                d_result, stream=None):
+        check(self._lib.pir_engine_answer_shamir_queue_dev(self._h, d_keys, key_pitch, key_stride,
+                                                           num_keys, rec0, nrec, d_result, stream),
+              "answer_shamir_queue_dev")
+
+    def reserve_shamir_queue(self, num_keys):
+        """Pre-size the work buffers for Shamir queues of up to num_keys keys (no allocation
+        inside later answer_shamir_queue[_dev] calls)."""
+        check(self._lib.pir_engine_reserve_shamir_queue(self._h, num_keys),
+              "reserve_shamir_queue")
+
     @property
     def woodruff_m(self):
         """The Woodruff key length M of this engine's 2^n records (pir_engine_woodruff_m)."""

@@ -18,6 +18,8 @@
  *   pir_engine_eval_all              evalAllOptimizedDPF                    dpf_tree.cpp:473-598
  *   pir_engine_answer_coefs[_dev]    runHollantiQuery / ...Thread           server.cpp:321-371
  *   pir_engine_answer_shamir[_dev]   runOptShamirDPFQuery / ...Thread       server.cpp:203-302
+ *   pir_engine_answer_shamir_queue[_dev]    K answers, 8 rounds per read of the shard
+ *   pir_engine_reserve_shamir_queue         (no counterpart: the reference answers one key)
  *   pir_engine_encode_hermite_*      generate_hermite_within_file           client.cpp:57-68
  *   pir_engine_shamir_response_len   calcShamirResponseLength               utils.cpp:140-143
  *   pir_engine_answer_woodruff[_dev] runWoodruffQueryThread (value answer)  server.cpp:564-616
@@ -190,6 +192,31 @@ int pir_engine_answer_shamir(pir_engine_t *e, const uint8_t *const *keys, uint64
 /* device form: round a's key at d_keys + a * key_pitch; asynchronous on `stream` */
 int pir_engine_answer_shamir_dev(pir_engine_t *e, const uint8_t *d_keys, uint64_t key_pitch,
                                  uint64_t rec0, uint64_t nrec, uint8_t *d_result, void *stream);
+/* A queue of num_keys independent Shamir queries over the records [rec0, rec0 + nrec): key k's
+ * round a at d_keys + k * key_stride + a * key_pitch (any alignment; the host form takes
+ * num_keys * num_rounds pointers, key-major), results num_keys x num_rounds x response_len bytes
+ * back to back, result k byte for byte what pir_engine_answer_shamir[_dev] gives for key k and
+ * the same range.  The refusals are those of the single answer; num_keys < 0 and, with num_keys
+ * > 0, null pointers are PIR_EINVAL; num_keys == 0 touches nothing, nrec == 0 zeroes every
+ * result.  A Byzantine engine answers the whole-domain queue with random bytes, fresh for each
+ * key, and every other range honestly.  A shared queue takes the num_keys * num_rounds rounds as
+ * independent virtual keys in ceil(K R / 8) groups of as equal sizes as possible (20 -> 7 + 7 +
+ * 6); a group's 8 key bytes of a matrix row or column are one 64-bit word, each of the two value
+ * passes reads the value rows once for the group (a transposed four-Russians fold per matrix row
+ * / column, the sums stored straight into the responses), and one 8-round scan reads the Hermite
+ * rows once.  $PIR_SH_SHARE, read at engine creation: 0 never shares (the single answers back to
+ * back on the stream), unset or 1 follows the measured policy (Queued Shamir queries
+ * share shard passes), 2 shares every queue of two or more virtual keys over records of at least
+ * 256 bytes (narrower records always run unshared); $PIR_SH_G overrides the slots per pass (2, 4
+ * or 8; default 8).  The device form is asynchronous on `stream`. */
+int pir_engine_answer_shamir_queue_dev(pir_engine_t *e, const uint8_t *d_keys, uint64_t key_pitch,
+                                       uint64_t key_stride, int num_keys, uint64_t rec0,
+                                       uint64_t nrec, uint8_t *d_result, void *stream);
+int pir_engine_answer_shamir_queue(pir_engine_t *e, const uint8_t *const *keys, int num_keys,
+                                   uint64_t rec0, uint64_t nrec, uint8_t *results);
+/* pre-size everything the queue touches for up to num_keys keys, so that a later queue call
+ * allocates nothing */
+int pir_engine_reserve_shamir_queue(pir_engine_t *e, int num_keys);
 /* the Hermite rows [N, 2N) of a Shamir engine (client.cpp:57-68, 103-107): row N + r = XOR over
  * odd j, 1 <= j < k, of gf_pow(party, j - 1) * part j of file r -- the formal derivative of the
  * within-file polynomial that pir_engine_encode_within_* evaluates; rows past num_files are
@@ -405,7 +432,10 @@ int pir_engine_memcpy_d2h(pir_engine_t *e, void *h_dst, const void *d_src, size_
  * an unshared queue records what its single answers record.  A shared queue of
  * explicit-coefficient, multiparty or covering-design queries (fused = 9) has the same one event
  * set with its share kernel in the coefficient kernel's place; the single answers of these modes
- * record none. */
+ * record none.  A shared Shamir queue (fused = 10) has one event set: launch = start -> the
+ * responses zeroed, scan = the first key table -> the end of the last group's Hermite scan,
+ * reduce = the last group's k_reduce and totals kernels; an unshared one records what its single
+ * answers record. */
 typedef struct {
     char name[32];
     float ms;

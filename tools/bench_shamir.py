@@ -11,6 +11,26 @@ read once); the answer's three passes (rows, strips, Hermite scan) are 3 reads o
 
     python tools/bench_shamir.py [--log-records 24] [--record-bytes 1024] [--rounds 1,2]
                                  [--iters 10] [--warmup 3]
+
+--queue measures queues of one-round Shamir queries instead (pir_engine_answer_shamir_queue_dev;
+the knobs are read at engine creation, so every leg has its own engine over the same shard
+bytes), for each queue length of --queue-lengths (default 2,4,8,20):
+
+  shared       $PIR_SH_SHARE=2: 8 virtual keys per read of the value rows and of the Hermite rows
+  shared_rx4   the same with the Rx pass / the Ry pass / both on k_shamir_rows / k_shamir_strips,
+  shared_ry4   up to 4 virtual keys per launch ($PIR_SH_PASS = 2 / 1 / 0, read per answer): a
+  shared_rxy4  transposed value pass against the four-round kernel in its place
+  unshared     $PIR_SH_SHARE=0: the single answers back to back
+  parent       --parent-lib PATH, the parent commit's library built into a second directory: K
+               back-to-back pir_engine_answer_shamir_dev calls on one stream
+  rounds4      a 4-round engine over the same bytes answering 4 keys per single call (the queued
+               keys taken as rounds: what k_shamir_rows / k_shamir_strips<4> give)
+
+and prints ONE JSON line: per queue length and leg the median, min and max ms and ms per key,
+the largest max - min spread of any leg, shared against parent, the gain of each transposed
+pass, and `shared_equals_unshared`, a byte comparison of every leg's answers at full size.
+
+    python tools/bench_shamir.py --queue [--parent-lib DIR/libpir_engine.so] [--queue-lengths 2,4,8,20]
 """
 import argparse
 import ctypes
@@ -60,6 +80,99 @@ class Events:
         return float(ms.value)
 
 
+def queue_bench(a):
+    from bench_woodruff import other_library_engine
+    n, efs = a.log_records, a.record_bytes
+    N = 1 << n
+    x = (n + 1) // 2
+    klen = (1 << x) + (1 << (n - x))
+    rl = pir.shamir_response_len(n, efs)
+    lengths = [int(v) for v in a.queue_lengths.split(",")]
+    kmax = (max(lengths) + 3) // 4 * 4
+    ev = Events(hip_runtime())
+    keys = np.random.default_rng(6).integers(0, 256, (kmax, klen), dtype=np.uint8)
+    engines, bufs = {}, {}
+    for leg, env in (("shared", {"PIR_SH_SHARE": "2"}), ("unshared", {"PIR_SH_SHARE": "0"})):
+        os.environ.update(env)
+        engines[leg] = pir.Engine(2, 1, n + 1, efs, 1)
+        for k in env:
+            del os.environ[k]
+    if a.parent_lib:
+        engines["parent"] = other_library_engine(a.parent_lib, 2, 1, n + 1, efs, 1)
+    engines["rounds4"] = pir.Engine(2, 1, n + 1, efs, 4)
+    for leg, e in engines.items():
+        e.fill_shard_random(16)
+        bufs[leg] = (e.alloc_dev(kmax * klen), e.alloc_dev(kmax * rl))
+        e.h2d(bufs[leg][0], keys.reshape(-1))
+        if leg in ("shared", "unshared"):
+            e.reserve_shamir_queue(kmax)
+    # the shared engine also serves the legs with one value pass on the 4-round kernels
+    # ($PIR_SH_PASS is read per answer)
+    passes = {"shared": None, "shared_rx4": "2", "shared_ry4": "1", "shared_rxy4": "0"}
+    legs = [l for l in ("shared", "shared_rx4", "shared_ry4", "shared_rxy4", "unshared", "parent",
+                        "rounds4") if l in engines or l in passes]
+    eng = {l: engines["shared" if l in passes else l] for l in legs}
+
+    def run(leg, K):
+        e = eng[leg]
+        d_k, d_r = bufs["shared" if leg in passes else leg]
+        if leg == "parent":
+            for k in range(K):
+                e.answer_shamir_dev(d_k + k * klen, klen, 0, N, d_r + k * rl)
+        elif leg == "rounds4":   # the queued keys taken as rounds, 4 per single answer
+            for k in range(0, K, 4):
+                e.answer_shamir_dev(d_k + k * klen, klen, 0, N, d_r + k * rl)
+        else:
+            if passes.get(leg):
+                os.environ["PIR_SH_PASS"] = passes[leg]
+            try:
+                e.answer_shamir_queue_dev(d_k, klen, klen, K, 0, N, d_r)
+            finally:
+                os.environ.pop("PIR_SH_PASS", None)
+
+    out = {"bench": "shamir_queue", "log_records": n, "record_bytes": efs, "key_len": klen,
+           "iters": a.iters, "warmup": a.warmup, "value_bytes": N * efs,
+           "parent_lib": bool(a.parent_lib), "queues": {}}
+    same, spread = True, 0.0
+    for K in lengths:
+        got = {}
+        for leg in legs:
+            run(leg, K)
+            eng[leg].sync()
+            got[leg] = eng[leg].d2h(bufs["shared" if leg in passes else leg][1], K * rl).copy()
+        same = same and all(np.array_equal(got["shared"], g) for g in got.values())
+        for _ in range(a.warmup):
+            for leg in legs:
+                run(leg, K)
+        for e in engines.values():
+            e.sync()
+        ms = {leg: [] for leg in legs}
+        for _ in range(a.iters):
+            for leg in legs:
+                ms[leg].append(ev.time(eng[leg].stream, lambda: run(leg, K)))
+        q = {}
+        for leg, v in ms.items():
+            med = statistics.median(v)
+            q[leg] = {"ms": round(med, 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                      "spread": round(max(v) - min(v), 4), "ms_per_key": round(med / K, 4)}
+            spread = max(spread, max(v) - min(v))
+        out["queues"][str(K)] = q
+    out["shared_equals_unshared"] = bool(same)
+    out["largest_spread_ms"] = round(spread, 4)
+    for K in lengths:
+        q = out["queues"][str(K)]
+        if a.parent_lib:
+            q["parent_minus_shared_ms"] = round(q["parent"]["ms"] - q["shared"]["ms"], 4)
+            q["shared_beats_parent"] = bool(q["parent"]["ms"] - q["shared"]["ms"] > spread)
+        # a transposed value pass against the 4-round kernel in its place: the other passes of
+        # the two legs are the same launches
+        q["rx_transposed_gain_ms"] = round(q["shared_rx4"]["ms"] - q["shared"]["ms"], 4)
+        q["ry_transposed_gain_ms"] = round(q["shared_ry4"]["ms"] - q["shared"]["ms"], 4)
+    for e in engines.values():
+        e.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-records", type=int, default=24)
@@ -67,7 +180,12 @@ def main():
     ap.add_argument("--rounds", default="1,2")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--queue", action="store_true")
+    ap.add_argument("--queue-lengths", default="2,4,8,20")
+    ap.add_argument("--parent-lib", default="")
     a = ap.parse_args()
+    if a.queue:
+        return queue_bench(a)
     n, efs = a.log_records, a.record_bytes
     N = 1 << n
     x = (n + 1) // 2
