@@ -118,6 +118,9 @@ PROTOTYPES = {
     "pir_engine_reserve_woodruff_queue": (_I, [_P, _I]),
     "pir_engine_answer_woodruff_deriv": (_I, [_P, _P, _U64, _U64, _U64, _P]),
     "pir_engine_answer_woodruff_deriv_dev": (_I, [_P, _P, _U64, _U64, _U64, _P, _P]),
+    "pir_engine_answer_woodruff_deriv_queue": (_I, [_P, _P, _U64, _I, _U64, _U64, _P]),
+    "pir_engine_answer_woodruff_deriv_queue_dev": (_I, [_P, _P, _U64, _I, _U64, _U64, _P, _P]),
+    "pir_engine_reserve_woodruff_deriv_queue": (_I, [_P, _I]),
     "pir_engine_answer_mp": (_I, [_P, _P, _U64, _I, _I, _I, _I, _P]),
     "pir_engine_answer_mp_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "pir_engine_mp_num_keys": (_I, [_I, _I]),

@@ -740,6 +740,12 @@ int pir_engine_create(const pir_engine_config* cfg, pir_engine_t** out) {
     if (shs && shs[0]) e->sh_share = std::max(0, std::min(2, atoi(shs)));
     const char* shg = getenv("PIR_SH_G");
     if (shg && shg[0]) e->sh_group = atoi(shg) >= 8 ? 8 : (atoi(shg) >= 4 ? 4 : 2);
+    // $PIR_WDD_SHARE / $PIR_WDD_G: queued Woodruff derivative keys per shard pass
+    // (woodruff_deriv_group)
+    const char* wds = getenv("PIR_WDD_SHARE");
+    if (wds && wds[0]) e->wdd_share = std::max(0, std::min(2, atoi(wds)));
+    const char* wdg = getenv("PIR_WDD_G");
+    if (wdg && wdg[0]) e->wdd_group = atoi(wdg) >= 8 ? 8 : (atoi(wdg) >= 4 ? 4 : 2);
     const char* bk = getenv("PIR_BATCH_KLAST");
     if (bk) e->batch_k_last = std::max(1, std::min(12, atoi(bk)));
     const int tile = pir::fused_tile(c.num_rounds, e->pitch, e->rows, e->num_cus);

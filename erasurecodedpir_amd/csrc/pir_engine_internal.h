@@ -176,6 +176,8 @@ struct pir_engine : eng::StreamSet {
   int gq_group = 0;             // $PIR_GQ_G: key slots per pass of a shared group queue (0: 8 / nrp)
   int sh_share = 1;             // $PIR_SH_SHARE: 0 never, 1 shamir_share_policy, 2 every queue of >= 2
   int sh_group = 0;             // $PIR_SH_G: virtual-key slots per pass of a shared Shamir queue (0: 8)
+  int wdd_share = 1;            // $PIR_WDD_SHARE: 0 never, 1 woodruff_deriv_share_policy, 2 every queue of >= 2
+  int wdd_group = 0;            // $PIR_WDD_G: key slots per pass of a shared Woodruff derivative queue (0: 8)
   uint64_t gq_key_bytes = 0;    // the longest sqrt(N) key a queue has staged (reserve_group_queue)
   int batch_scan_bpc = 2;       // scan workgroups per CU in batched answers ($PIR_BATCH_SCAN_BPC)
   int batch_k_last = -1;        // levels of the batched leaf stage (-1: make_plan's; $PIR_BATCH_KLAST)

@@ -27,7 +27,9 @@ constexpr int kNumPhases = 9;
 // (fused == 8) and a shared queue of explicit-coefficient or sqrt(N) DPF keys (fused == 9):
 // answer_group_queue; a shared Shamir queue (fused == 10): "launch" = start -> the responses
 // zeroed, "scan" = the first key table -> the end of the last group's Hermite scan, "reduce" =
-// the last group's k_reduce + k_shamir_totals
+// the last group's k_reduce + k_shamir_totals; a shared Woodruff derivative queue (fused == 11):
+// "launch" = start -> the responses zeroed, "scan" = the first key table -> the end of the last
+// group's columns pass, "reduce" = 0
 const char* const kQueryPhaseNames[] = {"launch", "scan", "reduce", "comm_fold", "total", "fused"};
 constexpr int kNumQueryPhases = 6;
 

@@ -1,5 +1,5 @@
-// pir_engine_woodruff.cpp -- the Woodruff mode: value answers, derivative answers, and the queue
-// of value queries that share shard passes.
+// pir_engine_woodruff.cpp -- the Woodruff mode: value answers, derivative answers, and the queues
+// of value queries and of derivative queries that share shard passes.
 #include "pir_engine_internal.h"
 
 using namespace eng;
@@ -196,6 +196,100 @@ int answer_woodruff_queue_locked(pir_engine* e, const uint8_t* d_keys, uint32_t 
                             });
 }
 
+// Key slots per pass of a queue of nk Woodruff derivative queries by default; 0: every key its
+// own answer (answer_woodruff_deriv_locked), back to back.  A pure function of the shape, on only
+// where the shared queue measured faster than the parent build's back-to-back single answers by
+// more than the largest spread of any leg of that run (tools/bench_woodruff.py --deriv-queue,
+// profiles/woodruff_deriv_queue/README.md); everything nobody measured stays off.
+int woodruff_deriv_share_policy(uint32_t pitch, uint64_t rows, int nk) {
+  // measured: queues of 2, 4, 8 and 20 keys over 2^20 and 2^24 rows of 1 KiB, 2^24 of 256 B and
+  // 2^22 of 2 KiB, 8 slots per pass.  2 keys: 1.5-3.4x the parent, 4: 2.9-6.3x, 8: 5.5-11.3x, 20
+  // (7 + 7 + 6): 4.7-10.1x, every one by more than the spread (the two passes of 8 slots cost
+  // 1.3 single answers at 2^24 x 1 KiB)
+  if (nk < 2) return 0;
+  const bool measured = (pitch == 1024 && rows >= (1ull << 20)) ||
+                        (pitch == 256 && rows >= (1ull << 24)) ||
+                        (pitch == 2048 && rows >= (1ull << 22));
+  return measured ? pir::kWdDerivSlots : 0;
+}
+
+// the slots per pass of a Woodruff derivative queue of nk keys (0: unshared).  $PIR_WDD_SHARE: 0
+// never shares, 1 (default) follows woodruff_deriv_share_policy, 2 shares every queue of two or
+// more keys on a shape k_woodruff_seg takes (records of >= 256 B); $PIR_WDD_G overrides the slots
+int woodruff_deriv_group(const pir_engine* e, int nk) {
+  if (e->wdd_share == 0 || nk < 2 || !pir::woodruff_seg_takes(e->pitch)) return 0;
+  int g = woodruff_deriv_share_policy(e->pitch, e->rows, nk);
+  if (g == 0 && e->wdd_share < 2) return 0;
+  if (g == 0) g = pir::kWdDerivSlots;
+  return e->wdd_group > 0 ? e->wdd_group : g;
+}
+// the one buffer a shared derivative queue touches: a group's interleaved key table (the single
+// answers need none); sized wherever some queue could share, whatever the policy says of nk keys
+int ensure_woodruff_deriv_queue(pir_engine* e, uint32_t M) {
+  if (e->wdd_share == 0 || !pir::woodruff_seg_takes(e->pitch)) return PIR_OK;
+  return e->d_cb.reserve((size_t)M * 8);
+}
+
+// Which pass hands a wave a long segment and then a short one (bit 0: rows, bit 1: columns); the
+// others hand the segments out longest first.  Longest first measured faster in both passes on
+// all four shapes (8 keys at 2^24 x 1 KiB: 7.99 ms against 8.71 / 8.76 for pairing in one pass
+// and 9.19 in both), so neither pairs.  $PIR_WDD_PAIR (diagnostics, read per answer) overrides it.
+constexpr int kWdDerivPair = 0;
+
+// A queue of nk Woodruff derivative queries over the records [rec0, rec0 + nrec): d_keys nk x M
+// bytes, d_result nk x (M + 1) x efs, result k what answer_woodruff_deriv_locked gives for key k.
+// Shared (woodruff_deriv_group > 0): one memset zeroes every response, the keys go into ceil(nk /
+// G) groups of as equal sizes as possible, and per group, all on s: the key table, the rows pass
+// (k_woodruff_seg<false>: R[a] stored into every key's record 1 + a), k_woodruff_totals once per
+// key (record 0 from the key's finished rows pass), the columns pass (k_woodruff_seg<true>: C[b]
+// XORed into record 1 + b).  Five-event layout, fused = 11: "launch" = start -> the responses
+// zeroed, "scan" = the first key table -> the end of the last group's columns pass, "reduce" = 0.
+// Unshared and empty ranges: the single answers back to back on s, each with its own slot.
+int answer_woodruff_deriv_queue_locked(pir_engine* e, const uint8_t* d_keys, uint32_t M, int nk,
+                                       uint64_t rec0, uint64_t nrec, uint8_t* d_result,
+                                       hipStream_t s) {
+  const auto& c = e->cfg;
+  const size_t out_bytes = (size_t)(M + 1) * c.record_bytes;
+  const int G = nrec ? woodruff_deriv_group(e, nk) : 0;
+  if (G == 0) {
+    for (int k = 0; k < nk; ++k)
+      if (int rc = answer_woodruff_deriv_locked(e, d_keys + (size_t)k * M, M, rec0, nrec,
+                                                d_result + (size_t)k * out_bytes, s))
+        return rc;
+    return PIR_OK;
+  }
+  if (int rc = ensure_woodruff_deriv_queue(e, M)) return rc;
+  e->ev = nullptr;
+  hipEvent_t* ev = nullptr;
+  if (!e->prof.empty()) {
+    ev = prof_slot(e, 11, 1, true);
+    HIP_TRY(hipEventRecord(ev[EV_START], s));
+  }
+  HIP_TRY(hipMemsetAsync(d_result, 0, (size_t)nk * out_bytes, s));
+  if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
+  const char* pv = getenv("PIR_WDD_PAIR");
+  const int pair = pv && pv[0] ? atoi(pv) & 3 : kWdDerivPair;
+  const uint64_t lo = rec0, hi = rec0 + nrec;
+  const int ngroups = (nk + G - 1) / G;
+  for (int q0 = 0, j = 0, ng = 0; q0 < nk; q0 += ng, ++j) {
+    ng = nk / ngroups + (j < nk % ngroups ? 1 : 0);
+    const uint8_t* const keys = d_keys + (size_t)q0 * M;
+    uint8_t* const out = d_result + (size_t)q0 * out_bytes;
+    HIP_TRY(pir::launch_woodruff_key_table(keys, M, ng, e->d_cb, s));
+    HIP_TRY(pir::launch_woodruff_seg(e->d_shard, e->pitch, c.record_bytes, e->d_cb, M, ng, lo, hi,
+                                     false, (pair & 1) != 0, out, s));
+    for (int g = 0; g < ng; ++g)
+      HIP_TRY(pir::launch_woodruff_totals(c.record_bytes, keys + (size_t)g * M, M, lo, hi,
+                                          out + (size_t)g * out_bytes, s));
+    HIP_TRY(pir::launch_woodruff_seg(e->d_shard, e->pitch, c.record_bytes, e->d_cb, M, ng, lo, hi,
+                                     true, (pair & 2) != 0, out, s));
+  }
+  e->last_fused = 11;
+  if (ev)
+    for (int i : {EV_SCAN_E, EV_RED, EV_END}) HIP_TRY(hipEventRecord(ev[i], s));
+  return PIR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -312,6 +406,49 @@ int pir_engine_answer_woodruff_deriv(pir_engine_t* e, const uint8_t* key, uint64
                                               e->d_shamir_res, e->stream));
   if (rc) return rc;
   return download(result, e->d_shamir_res, out_bytes, e->stream);
+}
+
+int pir_engine_answer_woodruff_deriv_queue_dev(pir_engine_t* e, const uint8_t* d_keys,
+                                               uint64_t key_len, int num_keys, uint64_t rec0,
+                                               uint64_t nrec, uint8_t* d_result, void* stream) {
+  if (int rc = check_queue_args(e, num_keys, d_keys, d_result)) return rc;
+  if (int rc = check_woodruff(e, key_len, rec0, nrec)) return rc;
+  if (num_keys == 0) return PIR_OK;
+  AnswerScope sc(e, stream);
+  if (sc.rc()) return sc.rc();
+  return sc.finish(answer_woodruff_deriv_queue_locked(e, d_keys, (uint32_t)key_len, num_keys, rec0,
+                                                      nrec, d_result, sc.stream()));
+}
+
+int pir_engine_answer_woodruff_deriv_queue(pir_engine_t* e, const uint8_t* keys, uint64_t key_len,
+                                           int num_keys, uint64_t rec0, uint64_t nrec,
+                                           uint8_t* results) {
+  if (int rc = check_queue_args(e, num_keys, keys, results)) return rc;
+  if (int rc = check_woodruff(e, key_len, rec0, nrec)) return rc;
+  if (num_keys == 0) return PIR_OK;
+  const size_t rb = (size_t)num_keys * (key_len + 1) * e->cfg.record_bytes;
+  AnswerScope sc(e);
+  if (sc.rc()) return sc.rc();
+  int rc = e->d_shamir_res.reserve(rb);
+  if (!rc) rc = stage(e->d_coef_stage, keys, (size_t)num_keys * key_len, hipMemcpyHostToDevice, e->stream);
+  if (rc) return rc;
+  rc = sc.finish(answer_woodruff_deriv_queue_locked(e, e->d_coef_stage, (uint32_t)key_len, num_keys,
+                                                    rec0, nrec, e->d_shamir_res, e->stream));
+  if (rc) return rc;
+  return download(results, e->d_shamir_res, rb, e->stream);
+}
+
+int pir_engine_reserve_woodruff_deriv_queue(pir_engine_t* e, int num_keys) {
+  if (!e || num_keys < 1) return fail(PIR_EINVAL, "bad argument");
+  if (int rc = check_woodruff(e, pir::wd_key_len(e->cfg.log_num_records), 0, 0)) return rc;
+  const uint32_t M = pir::wd_key_len(e->cfg.log_num_records);
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  int rc = ensure_woodruff_deriv_queue(e, M);
+  // the host form's staging
+  if (!rc) rc = e->d_coef_stage.reserve((size_t)num_keys * M);
+  if (!rc) rc = e->d_shamir_res.reserve((size_t)num_keys * (M + 1) * e->cfg.record_bytes);
+  return rc;
 }
 
 }  // extern "C"

@@ -106,4 +106,25 @@ hipError_t launch_woodruff_deriv(const uint8_t* rows, uint32_t pitch, uint32_t e
                                  const uint8_t* d_key, uint32_t M, uint64_t lo, uint64_t hi,
                                  uint8_t* out, hipStream_t s);
 
+// ---- queued derivative keys: up to kWdDerivSlots keys per pass (pir_woodruff_q.hip) ----------
+constexpr int kWdDerivSlots = 8;
+// the segmented pass takes records of at least one wave row (64 dwords)
+bool woodruff_seg_takes(uint32_t pitch);
+// d_keyT[j] (8-byte words, 8-byte aligned, M of them): byte g = key_g[j] for g < ng, zero above
+// (d_keys: M bytes each, back to back, any alignment)
+hipError_t launch_woodruff_key_table(const uint8_t* d_keys, uint32_t M, int ng, uint8_t* d_keyT,
+                                     hipStream_t s);
+// One derivative pass for the table's ng slots over the records [lo, hi): cols = false stores
+// R[a] = XOR_b key[b] * row(a, b) into response record 1 + a of every triangle row the range
+// touches, cols = true XORs C[b] = XOR_a key[a] * row(a, b) into record 1 + b; out = slot 0's
+// response (slot g's is (M + 1) * efs * g further), which the caller zeroed before the rows pass.
+// pair: a wave takes a long segment and then a short one (else: longest segments first).
+hipError_t launch_woodruff_seg(const uint8_t* rows, uint32_t pitch, uint32_t efs,
+                               const uint8_t* d_keyT, uint32_t M, int ng, uint64_t lo, uint64_t hi,
+                               bool cols, bool pair, uint8_t* out, hipStream_t s);
+// k_woodruff_totals alone: out[0] = XOR_a key[a] * out[1 + a] over the triangle rows the records
+// [lo, hi) touch, from one key's finished rows pass
+hipError_t launch_woodruff_totals(uint32_t efs, const uint8_t* d_key, uint32_t M, uint64_t lo,
+                                  uint64_t hi, uint8_t* out, hipStream_t s);
+
 }  // namespace pir

@@ -394,6 +394,33 @@ hipError_t launch_woodruff_deriv(const uint8_t* rows, uint32_t pitch, uint32_t e
   return hipGetLastError();
 }
 
+hipError_t launch_woodruff_totals(uint32_t efs, const uint8_t* d_key, uint32_t M, uint64_t lo,
+                                  uint64_t hi, uint8_t* out, hipStream_t s) {
+  if (lo >= hi) return hipSuccess;
+  if (M < 3 || hi > (uint64_t)M * (M - 1) / 2 || efs < 1) return hipErrorInvalidValue;
+  WdArgs A{};
+  A.key = d_key;
+  A.out = out;
+  A.lo = lo;
+  A.hi = hi;
+  A.a0 = wd_pair(M, lo).a;
+  A.a1 = wd_pair(M, hi - 1).a;
+  A.M = M;
+  A.efs = efs;
+  A.al = efs % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+  hipLaunchKernelGGL(k_woodruff_totals, dim3((efs + 15u) / 16u), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_woodruff_key_table(const uint8_t* d_keys, uint32_t M, int ng, uint8_t* d_keyT,
+                                     hipStream_t s) {
+  if (M < 3 || ng < 1 || ng > 8 || !d_keyT || reinterpret_cast<uintptr_t>(d_keyT) % 8 != 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_woodruff_key_table<8>), dim3((M + 255u) / 256u), dim3(256), 0, s, d_keys, M,
+                     ng, reinterpret_cast<uint2*>(d_keyT));
+  return hipGetLastError();
+}
+
 hipError_t launch_woodruff_coefs(const uint8_t* d_key, uint32_t M, int nrp, uint64_t lo,
                                  uint64_t hi, uint8_t* d_c, hipStream_t s) {
   if (lo >= hi) return hipSuccess;

@@ -389,6 +389,38 @@ class Engine:
         check(self._lib.pir_engine_reserve_woodruff_queue(self._h, num_keys),
               "reserve_woodruff_queue")
 
+    def answer_woodruff_deriv_queue(self, keys, rec0=0, nrec=None):
+        """A queue of independent Woodruff derivative queries over the records [rec0, rec0 +
+        nrec): keys is a list of keys or a (K, woodruff_m) array -> (K, woodruff_m + 1,
+        record_bytes) uint8, answer k what answer_woodruff_deriv gives for key k.  Where it
+        measured faster the queued keys share the two passes over the shard (8 keys per read of
+        it; $PIR_WDD_SHARE, $PIR_WDD_G: include/pir_engine.h), else each key has its own answer,
+        back to back."""
+        ks = [np.asarray(k, np.uint8).reshape(-1) for k in keys]
+        nk = len(ks)
+        key_len = ks[0].size if nk else self.woodruff_m
+        if any(k.size != key_len for k in ks):
+            raise _lib.PirError("answer_woodruff_deriv_queue: keys of different lengths")
+        k = np.ascontiguousarray(np.concatenate(ks)) if nk else np.zeros(1, np.uint8)
+        nrec = self.num_rows - rec0 if nrec is None else nrec
+        out = np.empty((nk, key_len + 1, self.record_bytes), np.uint8)
+        check(self._lib.pir_engine_answer_woodruff_deriv_queue(
+            self._h, k.ctypes.data_as(ctypes.c_void_p), key_len, nk, rec0, nrec,
+            out.ctypes.data_as(ctypes.c_void_p)), "pir_engine_answer_woodruff_deriv_queue")
+        return out
+
+    def answer_woodruff_deriv_queue_dev(self, d_keys, key_len, num_keys, rec0, nrec, d_result,
+                                        stream=None):
+        check(self._lib.pir_engine_answer_woodruff_deriv_queue_dev(
+            self._h, d_keys, key_len, num_keys, rec0, nrec, d_result, stream),
+            "answer_woodruff_deriv_queue_dev")
+
+    def reserve_woodruff_deriv_queue(self, num_keys):
+        """Pre-size the work buffers for Woodruff derivative queues of up to num_keys keys (no
+        allocation inside later answer_woodruff_deriv_queue[_dev] calls)."""
+        check(self._lib.pir_engine_reserve_woodruff_deriv_queue(self._h, num_keys),
+              "reserve_woodruff_deriv_queue")
+
     def answer_mp(self, key, p, t, thread_num=0, num_threads=1):
         """Multiparty sqrt(N) DPF answer (runOptimizedMultiPartyDPFQuery[Thread], src/c/
         server.cpp:136-176, :384-430): the key's NUM_RSS_KEYS shares of every record (the

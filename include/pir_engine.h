@@ -26,6 +26,8 @@
  *   pir_engine_answer_woodruff_deriv[_dev]  ... with WOODRUFF_DERIVATIVE    server.cpp:618-644
  *   pir_engine_answer_woodruff_queue[_dev]  K value answers, 8 keys per read of the shard
  *   pir_engine_reserve_woodruff_queue       (no counterpart: the reference answers one key)
+ *   pir_engine_answer_woodruff_deriv_queue[_dev]  K derivative answers, 8 keys per read
+ *   pir_engine_reserve_woodruff_deriv_queue (no counterpart: the reference answers one key)
  *   pir_engine_woodruff_m            calcWoodruffKeyLength / WOODRUFF_M     params.cpp:621-628
  *   pir_engine_woodruff_pair         makeCombi(M, 2)[i] - 1                 params.cpp:629-640
  *   pir_engine_answer_mp[_dev]       runOptimizedMultiPartyDPFQuery[Thread] server.cpp:136-176,
@@ -277,6 +279,30 @@ int pir_engine_answer_woodruff_queue(pir_engine_t *e, const uint8_t *keys, uint6
 /* pre-size everything the queue touches for up to num_keys keys, so that a later queue call
  * allocates nothing (as pir_engine_reserve_queue does for tree queues) */
 int pir_engine_reserve_woodruff_queue(pir_engine_t *e, int num_keys);
+/* A queue of num_keys independent Woodruff derivative queries over the records [rec0, rec0 +
+ * nrec): keys of key_len = M bytes back to back (any alignment), results num_keys x (M + 1) x
+ * record_bytes back to back, result k byte for byte what pir_engine_answer_woodruff_deriv[_dev]
+ * gives for key k and the same range.  The refusals are those of the single answer; num_keys < 0
+ * and, with num_keys > 0, null pointers are PIR_EINVAL; num_keys == 0 touches nothing, nrec == 0
+ * zeroes every result.  A shared queue goes into ceil(K / G) groups of as equal sizes as possible
+ * (20 -> 7 + 7 + 6); a group's 8 key bytes of an index are one 64-bit word, and each of the two
+ * passes reads the shard once for the group: a transposed four-Russians fold per triangle row /
+ * column, every key's sum put straight into its response (the rows pass stores, the columns pass
+ * XORs into that), the totals kernel once per key between the two.  $PIR_WDD_SHARE, read at
+ * engine creation: 0 never shares (the single answers back to back on the stream), unset or 1
+ * follows the measured policy (Queued Woodruff derivative queries share shard passes),
+ * 2 shares every queue of two or more keys over records of at least 256 bytes (narrower records
+ * always run unshared); $PIR_WDD_G overrides the slots per pass (2, 4 or 8; default 8).  The
+ * device form is asynchronous on `stream`. */
+int pir_engine_answer_woodruff_deriv_queue_dev(pir_engine_t *e, const uint8_t *d_keys,
+                                               uint64_t key_len, int num_keys, uint64_t rec0,
+                                               uint64_t nrec, uint8_t *d_result, void *stream);
+int pir_engine_answer_woodruff_deriv_queue(pir_engine_t *e, const uint8_t *keys, uint64_t key_len,
+                                           int num_keys, uint64_t rec0, uint64_t nrec,
+                                           uint8_t *results);
+/* pre-size everything the queue touches for up to num_keys keys (the key table, the host form's
+ * key and result staging), so that a later queue call allocates nothing */
+int pir_engine_reserve_woodruff_deriv_queue(pir_engine_t *e, int num_keys);
 /* the tile (records) of the single-launch path that answers this engine's whole domain when
  * $PIR_WD_FUSED selects it (k_query's Woodruff mode), 0 where its shape is not served and every
  * answer goes through the coefficient kernel + scan */
@@ -435,7 +461,9 @@ int pir_engine_memcpy_d2h(pir_engine_t *e, void *h_dst, const void *d_src, size_
  * record none.  A shared Shamir queue (fused = 10) has one event set: launch = start -> the
  * responses zeroed, scan = the first key table -> the end of the last group's Hermite scan,
  * reduce = the last group's k_reduce and totals kernels; an unshared one records what its single
- * answers record. */
+ * answers record.  A shared Woodruff derivative queue (fused = 11) has one event set: launch =
+ * start -> the responses zeroed, scan = the first key table -> the end of the last group's
+ * columns pass, reduce = 0; an unshared one records what its single answers record (7). */
 typedef struct {
     char name[32];
     float ms;

@@ -34,6 +34,15 @@ the largest max - min spread of any leg, shared against parent, and `shared_equa
 a byte comparison of the two legs' answers at full size.
 
     python tools/bench_woodruff.py --queue [--parent-lib DIR/libpir_engine.so] [--queue-lengths 2,4,8,20]
+
+--deriv-queue measures queues of Woodruff derivative queries the same way
+(pir_engine_answer_woodruff_deriv_queue_dev, M + 1 records per key): shared is $PIR_WDD_SHARE=2
+(8 keys per read of the shard in each of the two passes), unshared $PIR_WDD_SHARE=0, and parent K
+back-to-back pir_engine_answer_woodruff_deriv_dev calls of the parent commit's library.
+--pair-legs adds shared_pair0 .. 3: the shared engine with $PIR_WDD_PAIR forced (which pass hands
+a wave a long segment and then a short one; bit 0 the rows pass, bit 1 the columns pass).
+
+    python tools/bench_woodruff.py --deriv-queue [--parent-lib DIR/libpir_engine.so] [--pair-legs]
 """
 import argparse
 import ctypes
@@ -75,7 +84,10 @@ def queue_bench(a):
     ev = Events(hip_runtime())
     keys = np.random.default_rng(5).integers(0, 256, (kmax, M), dtype=np.uint8)
     engines, bufs = {}, {}
-    for leg, env in (("shared", {"PIR_WD_SHARE": "2"}), ("unshared", {"PIR_WD_SHARE": "0"})):
+    deriv = a.deriv_queue
+    knob = "PIR_WDD_SHARE" if deriv else "PIR_WD_SHARE"
+    rb = (M + 1) * efs if deriv else efs      # result bytes per key
+    for leg, env in (("shared", {knob: "2"}), ("unshared", {knob: "0"})):
         os.environ.update(env)
         engines[leg] = pir.Engine(2, 1, n, efs, 1)
         for k in env:
@@ -84,39 +96,54 @@ def queue_bench(a):
         engines["parent"] = other_library_engine(a.parent_lib, 2, 1, n, efs, 1)
     for leg, e in engines.items():
         e.fill_shard_random(15)
-        bufs[leg] = (e.alloc_dev(kmax * M), e.alloc_dev(kmax * efs))
+        bufs[leg] = (e.alloc_dev(kmax * M), e.alloc_dev(kmax * rb))
         e.h2d(bufs[leg][0], keys.reshape(-1))
         if leg != "parent":
-            e.reserve_woodruff_queue(kmax)
+            (e.reserve_woodruff_deriv_queue if deriv else e.reserve_woodruff_queue)(kmax)
+
+    # --pair-legs: the shared engine again with the segment hand-out forced ($PIR_WDD_PAIR is read
+    # per answer): shared_pair0 longest first in both passes, 1 / 2 / 3 a long segment and then a
+    # short one per wave in the rows pass / the columns pass / both
+    legs = {leg: leg for leg in engines}
+    if deriv and a.pair_legs:
+        legs.update({"shared_pair%d" % p: "shared" for p in range(4)})
 
     def run(leg, K):
-        e, (d_k, d_r) = engines[leg], bufs[leg]
-        if leg == "parent":
+        e, (d_k, d_r) = engines[legs[leg]], bufs[legs[leg]]
+        if leg.startswith("shared_pair"):
+            os.environ["PIR_WDD_PAIR"] = leg[-1]
+            e.answer_woodruff_deriv_queue_dev(d_k, M, K, 0, N, d_r)
+            del os.environ["PIR_WDD_PAIR"]
+        elif leg == "parent":
+            one = e.answer_woodruff_deriv_dev if deriv else e.answer_woodruff_dev
             for k in range(K):
-                e.answer_woodruff_dev(d_k + k * M, M, 0, N, d_r + k * efs)
+                one(d_k + k * M, M, 0, N, d_r + k * rb)
+        elif deriv:
+            e.answer_woodruff_deriv_queue_dev(d_k, M, K, 0, N, d_r)
         else:
             e.answer_woodruff_queue_dev(d_k, M, K, 0, N, d_r)
 
-    out = {"bench": "woodruff_queue", "log_records": n, "record_bytes": efs, "key_len": M,
+    out = {"bench": "woodruff_deriv_queue" if deriv else "woodruff_queue", "log_records": n,
+           "record_bytes": efs, "key_len": M,
            "iters": a.iters, "warmup": a.warmup, "shard_bytes": N * efs,
            "parent_lib": bool(a.parent_lib), "queues": {}}
     same, spread = True, 0.0
     for K in lengths:
         got = {}
-        for leg in engines:
+        for leg in legs:
             run(leg, K)
-            engines[leg].sync()
-            got[leg] = engines[leg].d2h(bufs[leg][1], K * efs).copy()
+            engines[legs[leg]].sync()
+            got[leg] = engines[legs[leg]].d2h(bufs[legs[leg]][1], K * rb).copy()
         same = same and all(np.array_equal(got["shared"], g) for g in got.values())
         for _ in range(a.warmup):
-            for leg in engines:
+            for leg in legs:
                 run(leg, K)
         for e in engines.values():
             e.sync()
-        ms = {leg: [] for leg in engines}
+        ms = {leg: [] for leg in legs}
         for _ in range(a.iters):
-            for leg, e in engines.items():
-                ms[leg].append(ev.time(e.stream, lambda: run(leg, K)))
+            for leg in legs:
+                ms[leg].append(ev.time(engines[legs[leg]].stream, lambda: run(leg, K)))
         q = {}
         for leg, v in ms.items():
             med = statistics.median(v)
@@ -131,6 +158,7 @@ def queue_bench(a):
             q = out["queues"][str(K)]
             q["parent_minus_shared_ms"] = round(q["parent"]["ms"] - q["shared"]["ms"], 4)
             q["shared_beats_parent"] = bool(q["parent"]["ms"] - q["shared"]["ms"] > spread)
+            q["parent_over_shared"] = round(q["parent"]["ms"] / q["shared"]["ms"], 3)
     for e in engines.values():
         e.close()
     print(json.dumps(out))
@@ -144,10 +172,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-deriv", action="store_true")
     ap.add_argument("--queue", action="store_true")
+    ap.add_argument("--deriv-queue", action="store_true")
+    ap.add_argument("--pair-legs", action="store_true")
     ap.add_argument("--queue-lengths", default="2,4,8,20")
     ap.add_argument("--parent-lib", default="")
     a = ap.parse_args()
-    if a.queue:
+    if a.queue or a.deriv_queue:
         return queue_bench(a)
     n, efs = a.log_records, a.record_bytes
     N, M = 1 << n, pir.woodruff_m(n)
