@@ -162,6 +162,9 @@ PROTOTYPES = {
     # pir_client.h
     "pir_gen_keys": (_I, [_I, _I, _U64, _P, _I, _I, _P, _P]),
     "pir_final_cw": (None, [_I, _I, _I, _P]),
+    "pir_gen_hollanti_keys_dev": (_I, [_I, _U64, _P, _I, _I, _I, _I, _I, _P, _P, _U64, _U64, _U64,
+                                       _P]),
+    "pir_gen_hollanti_keys": (_I, [_I, _U64, _P, _I, _I, _I, _I, _I, _P, _P]),
     "pir_mac_files_dev": (_I, [_I, _P, _U64, _U64, _U32, _P, _P, _U64, _P]),
     "pir_mac_files_rows": (_I, [_I, _P, _U64, _U32, _P]),
     "pir_mac_check": (_I, [_P, _U32, _P]),
@@ -245,6 +248,7 @@ PROTOTYPES = {
                                     ctypes.POINTER(c_u8_p)]),
     "pirSetDevice": (None, [_I]),
     "pirClientTagFiles": (None, [ctypes.POINTER(CClient)]),
+    "pirClientHollantiKeygenOnGpu": (None, [_I]),
     "pirServerShardChanged": (None, [ctypes.POINTER(CServer)]),
     "pirServerSyncRows": (None, [ctypes.POINTER(CServer)]),
     "pirRunTreeQueryThreads": (None, [ctypes.POINTER(CServer), ctypes.c_void_p, ctypes.c_int,

@@ -1,6 +1,7 @@
 """Client-side helpers (include/pir_client.h): DPF key generation on the GPU, the finalCW
-values of generate_opt_DPF_tree_query (src/c/client.cpp:144-153) and the CheckMAC record tags
-(HMAC-SHA256 under a 16-byte key, client.cpp:29-31) computed on the GPU."""
+values of generate_opt_DPF_tree_query (src/c/client.cpp:144-153), the Hollanti coefficient
+vectors (genHollantiDPF, shamir_dpf.cpp:190-237) and the CheckMAC record tags (HMAC-SHA256
+under a 16-byte key, client.cpp:29-31) computed on the GPU."""
 import ctypes
 import os
 
@@ -35,6 +36,49 @@ def gen_keys(n, index, p, nq=1, fcw=None, rho=1, seeds=None, device=0):
                                    seeds.ctypes.data_as(ctypes.c_void_p),
                                    out.ctypes.data_as(ctypes.c_void_p)), "pir_gen_keys")
     return [out[j * kl:(j + 1) * kl].tobytes() for j in range(p)]
+
+
+def _hollanti_args(indices, seeds):
+    idx = np.ascontiguousarray(np.atleast_1d(indices), dtype=np.uint64)
+    K = idx.size
+    if seeds is None:
+        seeds = os.urandom(16 * K)  # a fresh secret per query, from the OS CSPRNG
+    sd = np.frombuffer(bytes(seeds), dtype=np.uint8).copy()
+    if sd.size != 16 * K:
+        raise ValueError("seeds holds 16 bytes per key")
+    return idx, K, sd
+
+
+def gen_hollanti_keys(num_records, indices, t, p, nq=1, rho=1, seeds=None, device=0):
+    """The coefficient vectors of K Hollanti queries (genHollantiDPF with an AES-CTR key stream,
+    include/pir_client.h), made on the GPU: a (p, K, nq, num_records) uint8 array, [q, k] what
+    party q + 1 answers for record indices[k].
+
+    seeds: 16 bytes per key, each the secret of one query; default os.urandom."""
+    idx, K, sd = _hollanti_args(indices, seeds)
+    out = np.zeros((p, K, nq, num_records), np.uint8)
+    check(_lib.load().pir_gen_hollanti_keys(device, num_records, idx.ctypes.data_as(ctypes.c_void_p),
+                                            K, t, p, nq, rho, sd.ctypes.data_as(ctypes.c_void_p),
+                                            out.ctypes.data_as(ctypes.c_void_p)),
+          "pir_gen_hollanti_keys")
+    return out
+
+
+def gen_hollanti_keys_dev(num_records, indices, t, p, d_keys, coef_pitch, key_stride, party_stride,
+                          nq=1, rho=1, seeds=None, device=0, stream=None):
+    """pir_gen_hollanti_keys_dev over device memory: party q, key k, round a, record x at
+    d_keys + q*party_stride + k*key_stride + a*coef_pitch + x (d_keys a device address: an
+    Engine.alloc_dev pointer or a torch tensor's data_ptr(), plus any offset); d_keys +
+    q*party_stride is what Engine.answer_coefs_queue_dev(coef_pitch, key_stride) reads.
+    Asynchronous on `stream` (a hipStream_t address; None: the null stream).  Returns the seeds
+    used (16 bytes per key; default os.urandom)."""
+    idx, K, sd = _hollanti_args(indices, seeds)
+    check(_lib.load().pir_gen_hollanti_keys_dev(
+        device, num_records, idx.ctypes.data_as(ctypes.c_void_p), K, t, p, nq, rho,
+        sd.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(int(d_keys)) if d_keys else None,
+        coef_pitch, key_stride, party_stride, ctypes.c_void_p(stream) if stream else None),
+        "pir_gen_hollanti_keys_dev")
+    return sd.tobytes()
 
 
 MAC_BYTES = 32

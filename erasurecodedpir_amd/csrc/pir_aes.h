@@ -394,6 +394,16 @@ __device__ __forceinline__ uint4 aes_ctr_block(const Tab& T, uint4 key, uint32_t
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// Row shape, one block of a long CTR stream: AES_key(BE128(ctr)) with the whole 32-bit counter
+// big-endian in bytes 12-15 (aes_ctr_block carries its low 8 bits in byte 15 alone, enough for
+// the 3 blocks of a tree node).  aes_ctr_row's one-block form: its first two rounds are full
+// rounds when NB = 1, so any counter word is right.
+__device__ __forceinline__ uint4 aes_ctr_block_be32(const Tab& T, uint4 key, uint32_t ctr) {
+  uint4 out[1];
+  aes_ctr_row<1, 4>(T, key, out, __builtin_bswap32(ctr));
+  return out[0];
+}
+
 // ---- column shape: 4 lanes (a DPP quad) per block, lane q = column q ----------------------
 template <int CTRL>
 __device__ __forceinline__ uint32_t qperm(uint32_t v) {

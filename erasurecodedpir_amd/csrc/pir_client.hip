@@ -6,6 +6,10 @@
 // the CWs its control bits select.  One 64-lane workgroup: 3p <= 51 lanes expand, lane 0
 // forms the CWs, every lane writes key bytes.
 //
+// The Hollanti coefficient vectors (pir_gen_hollanti_keys[_dev]) are here too: the argument
+// checks, and k_hollanti_keys (pir_coefs.hip) launched once per 16 keys with their seeds and
+// indices in the kernel arguments.
+//
 // The CheckMAC record tags (pir_mac_files_dev / _rows / pir_mac_check) are here too: the
 // argument checks and the staging of host rows around k_hmac_sha256_files (pir_mac.hip).
 #include <stdio.h>
@@ -20,6 +24,7 @@
 #include "../../include/pir_client.h"
 #include "../../include/pir_engine.h"
 #include "pir_aes.h"
+#include "pir_coefs.h"
 #include "pir_mac.h"
 
 namespace pir {
@@ -119,6 +124,46 @@ uint8_t gf_mul_h(uint8_t a, uint8_t b) {
   return r;
 }
 
+static_assert(kHollantiMaxParties == PIR_MAX_PARTIES && kHollantiMaxRounds == PIR_MAX_ROUNDS,
+              "k_hollanti_keys is unrolled for the engine's limits");
+
+// every refusal of pir_gen_hollanti_keys[_dev] that needs no device (the strides apart)
+bool hollanti_args_ok(uint64_t num_records, const uint64_t* indices, int num_keys, int t, int p,
+                      int nq, int rho, const uint8_t* seeds, const uint8_t* out) {
+  if (num_keys < 0 || t < 1 || t > 255 || nq < 1 || nq > PIR_MAX_ROUNDS || rho < 1 || rho > 255 ||
+      p < 1 || p > PIR_MAX_PARTIES || t + rho * nq > 255 || num_records == 0 ||
+      num_records > (1ull << 36))
+    return false;
+  if (num_keys > 0 && (!indices || !seeds || !out)) return false;
+  for (int k = 0; k < num_keys; ++k)
+    if (indices[k] >= num_records) return false;
+  return true;
+}
+
+// the launches of a checked call: 16 keys each, asynchronous on s
+int launch_hollanti(uint64_t num_records, const uint64_t* indices, int num_keys, int t, int p,
+                    int nq, int rho, const uint8_t* seeds, uint8_t* d_keys, uint64_t coef_pitch,
+                    uint64_t key_stride, uint64_t party_stride, hipStream_t s) {
+  HollantiBatch hb{};
+  for (int a = 0; a < nq; ++a)
+    for (int q = 0; q < p; ++q) {
+      uint8_t r = 1;  // (q + 1)^(t + (a + 1) rho - 1)
+      for (int e = 0; e < t + (a + 1) * rho - 1; ++e) r = gf_mul_h(r, (uint8_t)(q + 1));
+      hb.secpow[a][q] = r;
+    }
+  for (int k0 = 0; k0 < num_keys; k0 += kHollantiBatch) {
+    const int nk = std::min(kHollantiBatch, num_keys - k0);
+    for (int k = 0; k < nk; ++k) {
+      memcpy(hb.seed[k], seeds + 16 * (size_t)(k0 + k), 16);  // little-endian words (load_seed)
+      hb.index[k] = indices[k0 + k];
+    }
+    if (launch_hollanti_keys(hb, nk, num_records, t, p, nq, d_keys + (uint64_t)k0 * key_stride,
+                             coef_pitch, key_stride, party_stride, s) != hipSuccess)
+      return PIR_EHIP;
+  }
+  return PIR_OK;
+}
+
 // host threads that gather payloads and scatter tags ($PIR_GATHER_THREADS, as the engine's
 // staged copies)
 int host_threads() {
@@ -171,6 +216,52 @@ int pir_gen_keys(int device, int n, uint64_t index, const uint8_t* fcw, int p, i
   }
   if (d_fcw) (void)hipFree(d_fcw);
   if (d_seeds) (void)hipFree(d_seeds);
+  if (d_keys) (void)hipFree(d_keys);
+  (void)hipStreamDestroy(s);
+  return rc;
+}
+
+int pir_gen_hollanti_keys_dev(int device, uint64_t num_records, const uint64_t* indices,
+                              int num_keys, int t, int p, int nq, int rho, const uint8_t* seeds,
+                              uint8_t* d_keys, uint64_t coef_pitch, uint64_t key_stride,
+                              uint64_t party_stride, void* stream) {
+  if (!pir::hollanti_args_ok(num_records, indices, num_keys, t, p, nq, rho, seeds, d_keys) ||
+      coef_pitch < num_records || key_stride / (uint64_t)nq < coef_pitch ||
+      (num_keys > 0 && party_stride / (uint64_t)num_keys < key_stride))
+    return PIR_EINVAL;
+  if (!num_keys) return PIR_OK;
+  if (hipSetDevice(device) != hipSuccess) return PIR_EHIP;
+  return pir::launch_hollanti(num_records, indices, num_keys, t, p, nq, rho, seeds, d_keys,
+                              coef_pitch, key_stride, party_stride,
+                              static_cast<hipStream_t>(stream));
+}
+
+int pir_gen_hollanti_keys(int device, uint64_t num_records, const uint64_t* indices, int num_keys,
+                          int t, int p, int nq, int rho, const uint8_t* seeds, uint8_t* keys_out) {
+  if (!pir::hollanti_args_ok(num_records, indices, num_keys, t, p, nq, rho, seeds, keys_out))
+    return PIR_EINVAL;
+  if (!num_keys) return PIR_OK;
+  // device vectors at a pitch of whole 16-byte stores, copied back packed
+  const uint64_t pitch = (num_records + 15) & ~15ull, rows = (uint64_t)p * num_keys * nq;
+  if (hipSetDevice(device) != hipSuccess) return PIR_EHIP;
+  hipStream_t s;
+  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return PIR_EHIP;
+  uint8_t* d_keys = nullptr;
+  int rc = PIR_OK;
+  if (hipMalloc(&d_keys, (size_t)(rows * pitch)) != hipSuccess) {
+    rc = PIR_ENOMEM;
+  } else {
+    rc = pir::launch_hollanti(num_records, indices, num_keys, t, p, nq, rho, seeds, d_keys, pitch,
+                              nq * pitch, (uint64_t)num_keys * nq * pitch, s);
+    if (rc == PIR_OK) {
+      const hipError_t e =
+          pitch == num_records
+              ? hipMemcpyAsync(keys_out, d_keys, (size_t)(rows * pitch), hipMemcpyDeviceToHost, s)
+              : hipMemcpy2DAsync(keys_out, num_records, d_keys, pitch, num_records, rows,
+                                 hipMemcpyDeviceToHost, s);
+      if (e != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = PIR_EHIP;
+    }
+  }
   if (d_keys) (void)hipFree(d_keys);
   (void)hipStreamDestroy(s);
   return rc;

@@ -38,4 +38,21 @@ hipError_t launch_encode_hermite(const uint8_t* d_files, uint64_t file_pitch, ui
                                  uint64_t rows, uint64_t row0, uint32_t pitch, uint32_t efs,
                                  hipStream_t s);
 
+// The client's Hollanti coefficient vectors (pir_gen_hollanti_keys_dev, include/pir_client.h: the
+// key stream) for up to kHollantiBatch keys in one launch, the keys' seeds and indices and the
+// secret term's factors by value in the kernel arguments (nothing to stage or free).
+constexpr int kHollantiBatch = 16;
+constexpr int kHollantiMaxParties = 17;  // PIR_MAX_PARTIES
+constexpr int kHollantiMaxRounds = 16;   // PIR_MAX_ROUNDS
+struct HollantiBatch {
+  uint32_t seed[kHollantiBatch][4];  // little-endian words of the 16 seed bytes
+  uint64_t index[kHollantiBatch];
+  uint8_t secpow[kHollantiMaxRounds][kHollantiMaxParties + 3];  // (q+1)^(t + (a+1) rho - 1)
+};
+// party q, key k, round a, record x -> d_keys[q*party_stride + k*key_stride + a*coef_pitch + x],
+// x < num_records; no byte at or past num_records of a vector is written
+hipError_t launch_hollanti_keys(const HollantiBatch& hb, int num_keys, uint64_t num_records, int t,
+                                int p, int nq, uint8_t* d_keys, uint64_t coef_pitch,
+                                uint64_t key_stride, uint64_t party_stride, hipStream_t s);
+
 }  // namespace pir

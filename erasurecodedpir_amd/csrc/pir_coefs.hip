@@ -3,7 +3,10 @@
 // share bytes (what k_scan reads per record).  Reads are coalesced along i for each round; each
 // lane writes its record's nrp bytes (one 1/2/4/8/16-byte store).  HBM-bound: nq + nrp bytes
 // per record, against the record_bytes of shard the scan then reads.
+// Also here: the Hollanti-mode shard encode (k_encode_within) and the client's Hollanti
+// coefficient vectors themselves (k_hollanti_keys), which share its packed constant multiply.
 #include "pir_coefs.h"
+#include "pir_aes.h"
 #include "pir_transpose.h"
 
 #include <algorithm>
@@ -241,6 +244,96 @@ hipError_t launch_encode_hermite(const uint8_t* d_files, uint64_t file_pitch, ui
   for (int j = 1; j < k && j < 16; j += 2) co.c[j] = gf_pow_h(party, j - 1);
   return launch_encode_parts(co, d_files, file_pitch, num_files, file_bytes, k, d_shard, rows,
                              row0, pitch, efs, s);
+}
+
+// ---- k_hollanti_keys: the client's coefficient vectors of Hollanti queries -------------------
+// genHollantiDPF (shamir_dpf.cpp:190-237) with its random bytes from AES-128-CTR (pir_client.h:
+// the key stream).  One lane owns 16 consecutive records = AES block `item` of every stream:
+// per round it runs the t blocks of its item (top coefficient first), Horner's rule at the
+// points q + 1 on the packed bytes (the points are compile-time constants of the unrolled party
+// loop), and writes p x 16 bytes.  Grid y is the key of the launch; a block derives the t
+// stream keys of a round from the key's seed into LDS before its lanes walk the items.
+// 16-byte stores where the destination is aligned, the bytes below N alone at a vector's tail.
+__device__ __forceinline__ void xor_byte(uint4& v, uint32_t pos, uint32_t b) {
+  const uint32_t m = b << (8 * (pos & 3)), w = pos >> 2;
+  v.x ^= w == 0 ? m : 0u;
+  v.y ^= w == 1 ? m : 0u;
+  v.z ^= w == 2 ? m : 0u;
+  v.w ^= w == 3 ? m : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_hollanti_keys(HollantiBatch hb, uint64_t nrec, int t,
+                                                       int p, int nq, uint8_t* __restrict__ keys,
+                                                       uint64_t coef_pitch, uint64_t key_stride,
+                                                       uint64_t party_stride) {
+  __shared__ uint32_t tab[2 * 256 * 32];
+  __shared__ uint4 sk[256];  // the stream keys of one round (t <= 254)
+  load_tables_n<256>(tab);
+  const Tab T(tab);
+  const int k = blockIdx.y, tid = threadIdx.x;
+  const uint4 seed = make_uint4(hb.seed[k][0], hb.seed[k][1], hb.seed[k][2], hb.seed[k][3]);
+  const uint64_t index = hb.index[k], own = index >> 4;
+  const uint32_t pos = (uint32_t)(index & 15);
+  const uint64_t nitems = (nrec + 15) / 16;
+  uint8_t* const kbase = keys + (uint64_t)k * key_stride;
+  for (int a = 0; a < nq; ++a) {
+    __syncthreads();  // the tables are filled; the last round's stream keys are read
+    if (tid < t) sk[tid] = aes_ctr_block_be32(T, seed, (uint32_t)(a * t + tid));
+    __syncthreads();
+    for (uint64_t item = (uint64_t)blockIdx.x * 256 + tid; item < nitems;
+         item += (uint64_t)gridDim.x * 256) {
+      uint4 acc[kHollantiMaxParties];
+      const uint4 top = aes_ctr_block_be32(T, sk[t - 1], (uint32_t)item);
+#pragma unroll
+      for (int q = 0; q < kHollantiMaxParties; ++q) acc[q] = top;
+      for (int m = t - 2; m >= 0; --m) {
+        const uint4 r = aes_ctr_block_be32(T, sk[m], (uint32_t)item);
+#pragma unroll
+        for (int q = 0; q < kHollantiMaxParties; ++q)
+          if (q < p) acc[q] = xor4(gf_mul_const4_w(acc[q], (uint32_t)(q + 1)), r);
+      }
+      if (item == own) {  // the secret term: one record of one lane
+#pragma unroll
+        for (int q = 0; q < kHollantiMaxParties; ++q)
+          if (q < p) xor_byte(acc[q], pos, hb.secpow[a][q]);
+      }
+      const uint64_t x0 = 16 * item;
+      const int cnt = (int)(nrec - x0 < 16 ? nrec - x0 : 16);
+#pragma unroll
+      for (int q = 0; q < kHollantiMaxParties; ++q) {
+        uint8_t* dst = kbase + (uint64_t)q * party_stride + (uint64_t)a * coef_pitch + x0;
+        if (q >= p) {
+        } else if (cnt == 16 && ((uintptr_t)dst & 15) == 0) {
+          *reinterpret_cast<uint4*>(dst) = acc[q];
+        } else {
+#pragma unroll
+          for (int b = 0; b < 16; ++b)
+            if (b < cnt) dst[b] = (uint8_t)tr_byte(acc[q], b);
+        }
+      }
+    }
+  }
+}
+
+hipError_t launch_hollanti_keys(const HollantiBatch& hb, int num_keys, uint64_t num_records, int t,
+                                int p, int nq, uint8_t* d_keys, uint64_t coef_pitch,
+                                uint64_t key_stride, uint64_t party_stride, hipStream_t s) {
+  if (num_keys < 1 || num_keys > kHollantiBatch || t < 1 || t > 254 || p < 1 ||
+      p > kHollantiMaxParties || nq < 1 || nq > kHollantiMaxRounds || num_records == 0 ||
+      num_records > (1ull << 36) || coef_pitch < num_records)
+    return hipErrorInvalidValue;
+  const uint64_t nitems = (num_records + 15) / 16;
+  // every block fills the 64 KiB AES tables once, and two blocks fit a CU's LDS: one resident
+  // set of blocks over all the keys of the launch, the items strided
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return hipErrorInvalidDevice;
+  const uint64_t per_key = std::max<uint64_t>(1, (2 * (uint64_t)cus + num_keys - 1) / num_keys);
+  const dim3 grid((unsigned)std::min<uint64_t>((nitems + 255) / 256, per_key), (unsigned)num_keys);
+  hipLaunchKernelGGL(k_hollanti_keys, grid, dim3(256), 0, s, hb, num_records, t, p, nq, d_keys,
+                     coef_pitch, key_stride, party_stride);
+  return hipGetLastError();
 }
 
 }  // namespace pir

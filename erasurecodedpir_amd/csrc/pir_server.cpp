@@ -623,8 +623,10 @@ namespace pir_shim {
 
 HermiteEncodeFn g_encode_hermite = nullptr;
 const WoodruffHooks* g_woodruff = nullptr;
+HollantiKeygenFn g_hollanti_keygen = nullptr;
 
 int device() { return device_default(); }
+void random_bytes(uint8_t* buf, size_t len) { os_random(buf, len); }
 
 void with_engine(server* s, int nq, const std::function<void(pir_engine_t*)>& fn) {
   ShimState* st = state_of(s);
@@ -703,10 +705,15 @@ void assembleDPFTreeQueryResponses(client* c, uint8_t* erasureIndexList, uint8_t
   memcpy(output, acc.data(), FILE_SIZE_BYTES);
 }
 
-// client.cpp:499-552 (semi-honest, B == 0): the polynomial-PIR decode.  Round i peels the parts
-// recovered in earlier rounds off the shares (gf_pow(point, K + T - 1 + i - b)), then reads
+// client.cpp:499-552 (semi-honest, B == 0): the polynomial-PIR decode.  Round i's answers are
+// values of x^s * (part_0 + part_1 x + ...) + (a random polynomial of degree <= K+T-2), s = T +
+// (i+1)*RHO - 1 the round's secret coefficient (genHollantiDPF).  The round peels the i*RHO parts
+// recovered in earlier rounds off the shares (part K-1-b at gf_pow(point, s + K-1-b)), then reads
 // coefficients K+T+RHO-2-q (q < RHO) of the degree-(K+T+RHO-2) interpolant at every byte
-// position into part K-1-i-q; one Vandermonde inverse per round.  output = FILE_SIZE_BYTES.
+// position into part K-1-i*RHO-q; one Vandermonde inverse per round.  With RHO == 1 this is the
+// reference's arithmetic term by term; its own peel and destination for RHO > 1 ("FIX THIS",
+// client.cpp:524) count one part a round and decode garbage from the second round on.
+// output = FILE_SIZE_BYTES.
 void assembleHollantiResponses(client* c, uint8_t* erasureIndexList, uint8_t*** responses,
                                uint8_t* output) {
   (void)c;
@@ -728,18 +735,19 @@ void assembleHollantiResponses(client* c, uint8_t* erasureIndexList, uint8_t*** 
       pts[j] = (uint8_t)cur++;
     }
     const std::vector<uint8_t> inv = vandermonde_inverse(pts.data(), m);
-    std::vector<uint8_t> peel((size_t)nr * i);
+    const int np = i * RHO, sec = T + (i + 1) * RHO - 1;  // parts known; this round's coefficient
+    std::vector<uint8_t> peel((size_t)nr * np);
     for (int j = 0; j < nr; ++j)
-      for (int b = 0; b < i; ++b) peel[(size_t)j * i + b] = gf_pow_h(pts[j], K + T - 1 + i - b);
+      for (int b = 0; b < np; ++b) peel[(size_t)j * np + b] = gf_pow_h(pts[j], sec + K - 1 - b);
     for (int a = 0; a < efs; ++a) {
       for (int j = 0; j < nr; ++j) {
         uint8_t v = responses[j][i][a];
-        for (int b = 0; b < i; ++b)
-          v ^= gf_mul_h(acc[(size_t)(K - 1 - b) * efs + a], peel[(size_t)j * i + b]);
+        for (int b = 0; b < np; ++b)
+          v ^= gf_mul_h(acc[(size_t)(K - 1 - b) * efs + a], peel[(size_t)j * np + b]);
         sh[j] = v;
       }
       for (int q = 0; q < RHO; ++q) {
-        const int row = deg - q, dst = K - 1 - i - q;
+        const int row = deg - q, dst = K - 1 - np - q;
         uint8_t v = 0;
         for (int j = 0; j < m; ++j) v ^= gf_mul_h(sh[j], inv[(size_t)row * m + j]);
         if (dst >= 0) acc[(size_t)dst * efs + a] = v;
@@ -1544,9 +1552,11 @@ void generate_opt_DPF_tree_query(client* c, int index, uint8_t*** keys) {
 // [x == index]; keys[q][a][x] = its value at q + 1 (evalPoly, shamir_dpf.cpp:10-17, Horner).
 // The reference's evalPoly is called with degree t + RHO*NUM_ROUNDS on an array of that many
 // bytes and so reads one byte past the allocation as the top coefficient; the intended
-// polynomial (that byte 0) is computed here.
+// polynomial (that byte 0) is computed here.  After pirClientHollantiKeygenOnGpu(1) the vectors
+// come from the GPU instead (pir_server_hollanti.cpp).
 void generateHollantiQuery(client* c, int index, uint8_t*** keys) {
   (void)c;
+  if (pir_shim::g_hollanti_keygen) return pir_shim::g_hollanti_keygen(index, keys);
   const int p = NUM_PARTIES, nq = NUM_ROUNDS, t = T, rho = RHO;
   const long N = NUM_ENCODED_FILES;
   std::vector<uint8_t> rnd((size_t)N * t);

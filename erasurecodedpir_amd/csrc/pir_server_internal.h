@@ -1,10 +1,11 @@
 // pir_server_internal.h -- the seam between pir_server.cpp and the translation units that add
-// modes to the shim (pir_server_shamir.cpp).  Not part of the C ABI.
+// modes to the shim (pir_server_shamir.cpp, _woodruff, _mac, _hollanti).  Not part of the C ABI.
 //
 // pir_server.cpp names no engine entry point newer than its own modes need, so that it links
 // against a stub of the engine (tests/tsan); a mode's unit reaches the server's engine through
 // with_engine and hands pir_server.cpp what its setup needs through the hooks below.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <functional>
@@ -38,5 +39,12 @@ struct WoodruffHooks {
   int (*pair)(uint32_t m, uint64_t i, uint32_t* a, uint32_t* b);
 };
 extern const WoodruffHooks* g_woodruff;
+
+// generateHollantiQuery on the GPU (pir_gen_hollanti_keys), set by pirClientHollantiKeygenOnGpu
+// of pir_server_hollanti.cpp (nullptr, the default: the host loop of pir_server.cpp).
+using HollantiKeygenFn = void (*)(int index, uint8_t*** keys);
+extern HollantiKeygenFn g_hollanti_keygen;
+// the OS CSPRNG as pir_server.cpp draws key seeds (aborts on failure)
+void random_bytes(uint8_t* buf, size_t len);
 
 }  // namespace pir_shim

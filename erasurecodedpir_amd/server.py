@@ -368,6 +368,12 @@ def generateHollantiQuery(index, c=None):
     return keys
 
 
+def hollanti_keygen_on_gpu(on=True):
+    """pirClientHollantiKeygenOnGpu: generateHollantiQuery makes its vectors on the GPU
+    (pir_gen_hollanti_keys under a fresh seed per query); off, the default: the host loop."""
+    _lib.load().pirClientHollantiKeygenOnGpu(int(bool(on)))
+
+
 def mac(key16, msg):
     """utils.cpp:32-34: HMAC-SHA256 of msg under the 16-byte key (32 bytes)."""
     k = np.frombuffer(bytes(key16), np.uint8).copy()

@@ -5,6 +5,8 @@
  *   pir_gen_keys       genOptimizedDPF          dpf_tree.cpp:142-274 (root seeds supplied by the
  *                                               caller; the reference draws them with RAND_bytes)
  *   pir_final_cw       generate_opt_DPF_tree_query's finalCW values   client.cpp:144-153
+ *   pir_gen_hollanti_keys*  genHollantiDPF      shamir_dpf.cpp:190-237 (random bytes from an
+ *                                               AES-CTR stream under a caller-supplied seed)
  *   pir_mac_files_*    the CheckMAC record tags of initialize_client  client.cpp:29-31
  *   pir_mac_check      the client's check of a decoded record         benchmark.go:190-207
  */
@@ -23,6 +25,37 @@ int pir_gen_keys(int device, int n, uint64_t index, const uint8_t *fcw, int p, i
                  const uint8_t *root_seeds, uint8_t *keys_out);
 /* out[a*(p-1) + j-2] = gf_pow(j, rho*(a+1)) ^ 1 for j = 2..p, a < nq (GF(2^8)/0x11d) */
 void pir_final_cw(int p, int nq, int rho, uint8_t *out);
+
+/* ---- Hollanti (polynomial PIR, mode 3) coefficient vectors, generated on the GPU ----
+ * genHollantiDPF (shamir_dpf.cpp:190-237) with the intended polynomial: for key k (record
+ * indices[k], seed seeds + 16*k), party q < p, round a < nq and record x < num_records, over
+ * GF(2^8)/0x11d,
+ *   key[q][a][x] = (XOR_{m<t} rnd[a][m][x] * (q+1)^m) ^ ([x == index] * (q+1)^(t + (a+1)*rho - 1)).
+ * The key stream: with G(key, n) = the first n bytes of AES-128-CTR under `key`, keystream block
+ * j = AES_key(BE128(j)), j = 0, 1, ... (the reference's G, utils.cpp:37-51),
+ *   sk = G(seed, 16*nq*t),  rnd[a][m][x] = G(sk[16*(a*t + m), +16), num_records)[x].
+ * A seed is a secret of ONE query: the caller draws 16 fresh bytes per key from the OS CSPRNG
+ * (getrandom, os.urandom), never a counter or a constant -- two queries under one seed differ
+ * in the two records they ask for and nowhere else.
+ *
+ * party q, key k, round a, record x at d_keys[q*party_stride + k*key_stride + a*coef_pitch + x];
+ * d_keys + q*party_stride is then the d_coefs of pir_engine_answer_coefs_queue_dev(coef_pitch,
+ * key_stride) and, for one key, of pir_engine_answer_coefs_dev.  No byte at or past num_records
+ * of a vector is written; vectors at 16-byte aligned addresses are written with 16-byte stores.
+ * Asynchronous on `stream` (indices and seeds are read before the call returns).
+ * PIR_EINVAL, checked before any device call: null pointers with num_keys > 0, num_keys < 0,
+ * t < 1, nq < 1 or > PIR_MAX_ROUNDS, rho < 1, p < 1 or > PIR_MAX_PARTIES, t + rho*nq > 255,
+ * num_records == 0 or > 2^36 (the 32-bit block counter), an index >= num_records,
+ * coef_pitch < num_records, key_stride < nq*coef_pitch, party_stride < num_keys*key_stride.
+ * num_keys == 0 returns PIR_OK and touches nothing. */
+int pir_gen_hollanti_keys_dev(int device, uint64_t num_records, const uint64_t *indices,
+                              int num_keys, int t, int p, int nq, int rho,
+                              const uint8_t *seeds /* num_keys*16, host */, uint8_t *d_keys,
+                              uint64_t coef_pitch, uint64_t key_stride, uint64_t party_stride,
+                              void *stream);
+/* host form: keys_out packed (p, num_keys, nq, num_records); synchronous */
+int pir_gen_hollanti_keys(int device, uint64_t num_records, const uint64_t *indices, int num_keys,
+                          int t, int p, int nq, int rho, const uint8_t *seeds, uint8_t *keys_out);
 
 /* ---- record tags: HMAC-SHA256 under a 16-byte key (utils.cpp:32-34), computed on the GPU ---- */
 #define PIR_MAC_BYTES 32

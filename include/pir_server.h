@@ -293,6 +293,11 @@ void pirSetDevice(int device);
  * [PAYLOAD_SIZE_BYTES, +32) is recomputed under c->macKey on the GPU (pir_mac_files_rows).
  * Aborts if CHECK_MAC is 0. */
 void pirClientTagFiles(client *c);
+/* on != 0: generateHollantiQuery makes its vectors on the GPU (pir_gen_hollanti_keys under one
+ * fresh 16-byte seed from the OS CSPRNG per query: include/pir_client.h, the key stream) instead
+ * of the host loop; 0 (the default of a process): the host loop, its random bytes straight from
+ * the OS.  Either way a query has the structure genHollantiDPF gives it. */
+void pirClientHollantiKeygenOnGpu(int on);
 /* indexList rows were written by something other than encode_across_files_server: the next
  * query re-uploads the shard to HBM (encode_across_files_server does this implicitly).  After a
  * GPU setup, call pirServerSyncRows BEFORE writing the rows directly. */
