@@ -1,5 +1,6 @@
-// pir_bits.h -- bit-matrix transposes of the transposed four-Russians scan (pir_scan_t.hip).
-// Plain integer code, host and device (tests/test_bits_nibble.py checks it on the CPU).
+// pir_bits.h -- bit-matrix transposes of the transposed four-Russians scan (pir_seg_walk.h) and
+// the packed GF(2^8) "times alpha" every bit-plane fold ends with.  Plain integer code, host and
+// device (tests/test_bits_nibble.py and tests/test_bits_xtime.py check it on the CPU).
 #pragma once
 #include <stdint.h>
 
@@ -11,6 +12,11 @@
 #endif
 
 namespace pir {
+
+// 4 packed bytes times alpha in GF(2^8), poly 0x11d (coding.cpp:9-21): no carry crosses a byte
+PIR_HD uint32_t gf_xtime4(uint32_t x) {
+  return ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1du);
+}
 
 // swap the off-diagonal S x S blocks of rows a (block row 0) and b (block row 1): positions p
 // with (p & S) == 0 are selected by m

@@ -7,6 +7,7 @@
 // coefficient vectors themselves (k_hollanti_keys), which share its packed constant multiply.
 #include "pir_coefs.h"
 #include "pir_aes.h"
+#include "pir_bits.h"
 #include "pir_transpose.h"
 
 #include <algorithm>
@@ -135,15 +136,11 @@ struct WithinCoefs {
   uint8_t c[16];
 };
 
-__device__ __forceinline__ uint32_t xtime4_w(uint32_t x) {
-  return ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1du);
-}
-
 __device__ __forceinline__ uint4 gf_mul_const4_w(uint4 x, uint32_t c) {
   uint4 acc = make_uint4(0, 0, 0, 0);
   for (int b = 0; b < 8; ++b) {
     if (c & (1u << b)) acc = make_uint4(acc.x ^ x.x, acc.y ^ x.y, acc.z ^ x.z, acc.w ^ x.w);
-    x = make_uint4(xtime4_w(x.x), xtime4_w(x.y), xtime4_w(x.z), xtime4_w(x.w));
+    x = make_uint4(gf_xtime4(x.x), gf_xtime4(x.y), gf_xtime4(x.z), gf_xtime4(x.w));
   }
   return acc;
 }

@@ -16,6 +16,7 @@
 // HBM stream costs ~1 VALU op per byte.
 #include "pir_kernels.h"
 #include "pir_aes.h"
+#include "pir_bits.h"
 #include "pir_tree.h"
 #include "pir_m4r.h"
 #include "pir_mp.h"
@@ -346,12 +347,9 @@ __global__ __launch_bounds__(kExpThreads) void k_expand(
 }
 
 // ------------------------------------------------------------------------------------------
-// k_scan: per-workgroup partial answers over GF(2^8), poly 0x11d (coding.cpp:9-21)
+// k_scan: per-workgroup partial answers over GF(2^8), poly 0x11d (coding.cpp:9-21); the fold by
+// the alpha powers is gf_xtime4 (pir_bits.h)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t gf_xtime4(uint32_t x) {  // 4 packed bytes times alpha
-  return ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1du);
-}
-
 template <int VEC>
 struct Chunk {
   uint32_t v[VEC];

@@ -13,6 +13,7 @@
 // fold sum_k alpha^k Z_k once at the end, poly 0x11d) for up to kShamirRounds rounds at a time.
 // Every shape goes through these kernels: records of any efs >= 1 (rows are pitch = 16-byte
 // multiples apart, pad bytes zero), n >= 0, ranges that cut matrix rows.
+#include "pir_bits.h"
 #include "pir_shamir.h"
 
 #include <algorithm>
@@ -31,14 +32,11 @@ ShamirDims shamir_dims(int n, uint32_t efs) {
 
 namespace {
 
-__device__ __forceinline__ uint32_t xtime4_s(uint32_t x) {
-  return ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1du);
-}
 __device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) {
   return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
 }
 __device__ __forceinline__ uint4 xtime16(uint4 x) {
-  return make_uint4(xtime4_s(x.x), xtime4_s(x.y), xtime4_s(x.z), xtime4_s(x.w));
+  return make_uint4(gf_xtime4(x.x), gf_xtime4(x.y), gf_xtime4(x.z), gf_xtime4(x.w));
 }
 // x * c for a per-lane coefficient byte
 __device__ __forceinline__ uint4 gf_mul16(uint4 x, uint32_t c) {

@@ -7,15 +7,17 @@
 // Up to 8 virtual keys (the rounds of the queued keys) go through a pass together:
 //   k_shamir_key_table  kT[j] = the 8 keys' byte j as one 64-bit word (slot g = byte g, absent
 //                       slots zero): kyT = kT[0, X), kxT = kT[X, X + Y)
-//   k_shamir_seg        one wave per (segment, 64-dword column group): pir_scan_t.hip's transposed
+//   k_shamir_seg        one wave per (segment, 64-dword column group): the transposed
 //                       four-Russians fold over the segment's rows (the index from the shard's
 //                       bits, the nibble tables from the coefficient words; the cost per row does
 //                       not depend on the number of planes), the per-segment sums stored straight
-//                       into each virtual key's response record.  No slabs, no k_reduce.
+//                       into each virtual key's response record.  No slabs, no k_reduce.  The
+//                       fold, the way back to planes and the store are pir_seg_walk.h's seg_walk,
+//                       planes_out and seg_store; the kernel itself is the segment's geometry.
 //   k_shamir_coefs_g    the Hermite scan's record-major share rows c[i] = kxT[gamma_i] *
 //                       kyT[delta_i], byte-wise (two wd_gf_mul4)
-#include "pir_bits.h"
 #include "pir_kernels.h"
+#include "pir_seg_walk.h"
 #include "pir_shamir.h"
 #include "pir_woodruff.h"
 
@@ -23,16 +25,9 @@
 
 namespace pir {
 
-bool shamir_seg_takes(uint32_t pitch) { return pitch % 4 == 0 && pitch / 4 >= (uint32_t)kColGroupLanes; }
+bool shamir_seg_takes(uint32_t pitch) { return seg_takes(pitch); }
 
 namespace {
-
-constexpr int kSegThreads = 256;
-constexpr int kSegWaves = kSegThreads / 64;
-
-__device__ __forceinline__ uint32_t xtime4_q(uint32_t x) {  // 4 packed bytes times alpha
-  return ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1du);
-}
 
 __global__ __launch_bounds__(256) void k_shamir_key_table(const uint8_t* __restrict__ keys,
                                                           uint64_t key_pitch, uint64_t key_stride,
@@ -70,8 +65,7 @@ struct SegArgs {
 template <bool STRIDED>
 __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(kScanTWavesPerEU)))
 void k_shamir_seg(SegArgs A) {
-  constexpr int kTabBytes = 128;  // 16 entries of 8 bytes: aligned to its size, conflict free
-  __shared__ alignas(128) uint32_t tab[kSegWaves][16 * kTabBytes / 4];
+  __shared__ alignas(128) uint32_t tab[kSegWaves][FrTab<2>::kWords];
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t item = (uint64_t)blockIdx.x * kSegWaves + wv;
@@ -100,141 +94,18 @@ void k_shamir_seg(SegArgs A) {
   const uint8_t* const p0 = base + ra * stride;
   const uint32_t voff = (active ? dw : 0u) * 4u;  // inactive lanes: the row's first dword
   const uint2* const kw = A.kT + ra;
-  uint32_t* const tw = &tab[wv][0];
-
   uint32_t Zt[32][2];
-#pragma unroll
-  for (int j = 0; j < 32; ++j) Zt[j][0] = Zt[j][1] = 0;
-
-  // rows past the segment's last re-read its first and have zero coefficient words
-  auto load_rel = [&](uint32_t rel) __attribute__((always_inline)) {
-    const uint64_t off = (uint64_t)(rel < nrows ? rel : 0u) * stride;
-    return __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p0 + off + voff));
-  };
-  auto coefs64 = [&](uint32_t r0) __attribute__((always_inline)) {
-    const uint32_t rl = r0 + lane;
-    uint2 cw = make_uint2(0, 0);
-    if (rl < nrows) cw = kw[rl];
-    return cw;
-  };
-  // the chunk's 16 nibble tables, built lane-parallel as in k_scan_t
-  const uint32_t q2 = (lane & 1u) ? 0xffffffffu : 0u, q3 = (lane & 2u) ? 0xffffffffu : 0u;
-  auto build_tables = [&](const uint2& cw) __attribute__((always_inline)) {
-    uint32_t e[4][2];
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      const int s = (int)(d ? cw.y : cw.x);
-      const uint32_t w0 = (uint32_t)__builtin_amdgcn_update_dpp(0, s, 0x00, 0xf, 0xf, false);
-      const uint32_t w1 = (uint32_t)__builtin_amdgcn_update_dpp(0, s, 0x55, 0xf, 0xf, false);
-      const uint32_t w2 = (uint32_t)__builtin_amdgcn_update_dpp(0, s, 0xaa, 0xf, 0xf, false);
-      const uint32_t w3 = (uint32_t)__builtin_amdgcn_update_dpp(0, s, 0xff, 0xf, 0xf, false);
-      e[0][d] = (w2 & q2) ^ (w3 & q3);
-      e[1][d] = e[0][d] ^ w0;
-      e[2][d] = e[0][d] ^ w1;
-      e[3][d] = e[1][d] ^ w1;
-    }
-    __builtin_amdgcn_wave_barrier();  // the previous chunk's reads are issued (LDS keeps its order)
-    uint4* const dst = reinterpret_cast<uint4*>(tw) + lane * 2;
-    dst[0] = make_uint4(e[0][0], e[0][1], e[1][0], e[1][1]);
-    dst[1] = make_uint4(e[2][0], e[2][1], e[3][0], e[3][1]);
-    __builtin_amdgcn_wave_barrier();  // the wave's own tables: no workgroup barrier
-  };
-
-  const uint32_t nch = (nrows + 63) / 64;
-  uint32_t x[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) x[u] = load_rel((uint32_t)u);
-  uint2 cw = coefs64(0);
-  for (uint32_t cur = 0; cur < nch; ++cur) {
-    const uint32_t r0 = cur * 64;
-    const uint2 cwn = cur + 1 < nch ? coefs64(r0 + 64) : make_uint2(0, 0);  // in flight
-    const uint32_t nb = nrows - r0 < 64 ? nrows - r0 : 64;
-    build_tables(cw);
-    for (uint32_t j0 = 0; j0 < nb; j0 += 16) {
-      const char* const tj = reinterpret_cast<const char*>(tw) + j0 / 4 * kTabBytes;
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const uint32_t j = r0 + j0 + 8 * g;
-        uint32_t (&L)[4] = *reinterpret_cast<uint32_t(*)[4]>(&x[8 * g]);  // in place
-        uint32_t (&H)[4] = *reinterpret_cast<uint32_t(*)[4]>(&x[8 * g + 4]);
-        transpose4x32(L);
-        transpose4x32(H);
-        // k_scan_t's 8 software-pipelined steps of 4 bit positions: step s takes the even or odd
-        // nibbles of L[s / 2], H[s / 2] as entry byte offsets
-        const char* const tg = tj + g * (2 * kTabBytes);
-        uint2 ta[8], tb[8];
-        auto issue = [&](uint2 (&t)[8], int s) __attribute__((always_inline)) {
-          uint32_t lo = (s & 1) ? L[s >> 1] >> 1 : L[s >> 1] << 3;
-          uint32_t hi = (s & 1) ? H[s >> 1] >> 1 : H[s >> 1] << 3;
-          lo &= 0x0f0f0f0fu << 3;
-          hi &= 0x0f0f0f0fu << 3;
-          asm volatile("" : "+v"(lo), "+v"(hi));
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            t[2 * b] = *reinterpret_cast<const uint2*>(tg + ((lo >> (8 * b)) & 0xffu));
-            t[2 * b + 1] = *reinterpret_cast<const uint2*>(tg + kTabBytes + ((hi >> (8 * b)) & 0xffu));
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        };
-        auto fold = [&](const uint2 (&t)[8], int s) __attribute__((always_inline)) {
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            uint32_t (&z)[2] = Zt[8 * b + 4 * (s & 1) + (s >> 1)];
-            z[0] = __builtin_amdgcn_bitop3_b32(z[0], t[2 * b].x, t[2 * b + 1].x, 0x96);
-            z[1] = __builtin_amdgcn_bitop3_b32(z[1], t[2 * b].y, t[2 * b + 1].y, 0x96);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        };
-        issue(ta, 0);
-        issue(tb, 1);
-        fold(ta, 0);
-        issue(ta, 2);
-        fold(tb, 1);
-        issue(tb, 3);
-        fold(ta, 2);
-        issue(ta, 4);
-        fold(tb, 3);
-        issue(tb, 5);
-        fold(ta, 4);
-        issue(ta, 6);
-        fold(tb, 5);
-        issue(tb, 7);
-        fold(ta, 6);
-        fold(tb, 7);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) x[8 * g + r] = load_rel(j + 16 + r);
-        __builtin_amdgcn_sched_barrier(0);  // one group at a time (register pressure)
-      }
-    }
-    cw = cwn;
-  }
+  seg_walk(
+      p0, [&](uint32_t rel) __attribute__((always_inline)) { return (uint64_t)rel * stride; },
+      nrows, kw, voff, lane, &tab[wv][0], Zt);
 
   // back to planes, the fold by the powers of alpha, and each slot's dword into its response
   const uint32_t off = dw * 4u;
-  const bool in = active && off < A.efs;
-  uint8_t* const rec = A.out + (A.rec_base + seg) * A.efs + off;
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    uint32_t Y[32];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) Y[j] = Zt[j][d];
-    transpose32(Y);  // Y[q]: plane 32 d + q = (slot 4 d + q / 8, bit q % 8)
-#pragma unroll
-    for (int a4 = 0; a4 < 4; ++a4) {
-      const int a = 4 * d + a4;
-      uint32_t acc = Y[8 * a4 + 7];
-#pragma unroll
-      for (int b = 6; b >= 0; --b) acc = xtime4_q(acc) ^ Y[8 * a4 + b];
-      if (in && a < A.ng) {
-        uint8_t* const o = rec + (uint64_t)a * A.resp_len;
-        if (A.al4) {
-          *reinterpret_cast<uint32_t*>(o) = acc;
-        } else {  // records of efs % 4 != 0, or an unaligned response: bytewise
-          for (uint32_t t = 0; t < 4u && off + t < A.efs; ++t) o[t] = (uint8_t)(acc >> (8 * t));
-        }
-      }
-    }
-  }
+  const SegOut O{A.out + (A.rec_base + seg) * A.efs + off, A.resp_len, off, A.efs, A.ng, A.al4,
+                 active && off < A.efs};
+  planes_out<2, 8>(Zt, [&](int g, uint32_t acc) __attribute__((always_inline)) {
+    seg_store<false>(O, g, acc);
+  });
 }
 
 // two records per thread: one 16-byte store, the range's last odd record on its own

@@ -13,6 +13,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "pir_bits.h"
+
 namespace pir {
 
 struct WdPair {
@@ -68,7 +70,7 @@ __host__ __device__ inline uint32_t wd_gf_mul4(uint32_t a, uint32_t b) {
   for (int t = 0; t < 8; ++t) {
     const uint32_t m = (b >> t) & 0x01010101u;
     acc ^= a & ((m << 8) - m);  // m * 0xff: the lanes whose bit t of b is set
-    a = ((a & 0x7f7f7f7fu) << 1) ^ (((a >> 7) & 0x01010101u) * 0x1du);
+    a = gf_xtime4(a);
   }
   return acc;
 }

@@ -166,14 +166,11 @@ hipError_t coefs_g(const uint8_t* d_keys, uint32_t M, int ng, uint64_t lo, uint6
 }
 
 // ---- derivative answers (server.cpp:618-644) -------------------------------------------------
-__device__ __forceinline__ uint32_t xtime4_w(uint32_t x) {
-  return ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1du);
-}
 __device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) {
   return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
 }
 __device__ __forceinline__ uint4 xtime16(uint4 x) {
-  return make_uint4(xtime4_w(x.x), xtime4_w(x.y), xtime4_w(x.z), xtime4_w(x.w));
+  return make_uint4(gf_xtime4(x.x), gf_xtime4(x.y), gf_xtime4(x.z), gf_xtime4(x.w));
 }
 // Z[k] ^= x for the set bits k of this lane's coefficient c (the lanes of a wave hold different
 // triangle rows / columns, so the masks are per lane)

@@ -19,14 +19,9 @@
 
 namespace pir {
 
-bool woodruff_seg_takes(uint32_t pitch) {
-  return pitch % 4 == 0 && pitch / 4 >= (uint32_t)kColGroupLanes;
-}
+bool woodruff_seg_takes(uint32_t pitch) { return seg_takes(pitch); }
 
 namespace {
-
-constexpr int kSegThreads = 256;
-constexpr int kSegWaves = kSegThreads / 64;
 
 struct WdSegArgs {
   const uint8_t* rows;  // the shard: record i at rows + i * pitch
@@ -47,7 +42,7 @@ struct WdSegArgs {
 template <bool COLS>
 __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(kScanTWavesPerEU)))
 void k_woodruff_seg(WdSegArgs A) {
-  __shared__ alignas(128) uint32_t tab[kSegWaves][kSegTabWords];
+  __shared__ alignas(128) uint32_t tab[kSegWaves][FrTab<2>::kWords];
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t item = (uint64_t)blockIdx.x * kSegWaves + wv;
@@ -105,19 +100,9 @@ void k_woodruff_seg(WdSegArgs A) {
           [&](uint32_t rel) __attribute__((always_inline)) { return o0 + (uint64_t)rel * A.pitch; },
           nrows, kw, voff, lane, tw, Zt);
     }
-    uint8_t* const rec = A.out + (uint64_t)(1 + seg) * A.efs + off;
-    seg_planes_out(Zt, [&](int g, uint32_t acc) __attribute__((always_inline)) {
-      if (!in || g >= A.ng) return;
-      uint8_t* const o = rec + (uint64_t)g * A.resp_len;
-      if (A.al4) {
-        uint32_t* const w = reinterpret_cast<uint32_t*>(o);
-        *w = COLS ? *w ^ acc : acc;
-      } else {  // records of efs % 4 != 0, or an unaligned response: bytewise
-        for (uint32_t u = 0; u < 4u && off + u < A.efs; ++u) {
-          const uint8_t v = (uint8_t)(acc >> (8 * u));
-          o[u] = COLS ? (uint8_t)(o[u] ^ v) : v;
-        }
-      }
+    const SegOut O{A.out + (uint64_t)(1 + seg) * A.efs + off, A.resp_len, off, A.efs, A.ng, A.al4, in};
+    planes_out<2, 8>(Zt, [&](int g, uint32_t acc) __attribute__((always_inline)) {
+      seg_store<COLS>(O, g, acc);
     });
   }
 }
