@@ -35,6 +35,31 @@ PIR_HD void transpose4x32(uint32_t (&x)[4]) {
   bit_swap<1>(x[0], x[1], 0x55555555u); bit_swap<1>(x[2], x[3], 0x55555555u);
 }
 
+// The fold image (pir_scan_t.hip, k_fold_image): the shard's bits in the nibble-index form the
+// transposed scan looks tables up by, made once per shard.  The four dwords of rows 4B .. 4B + 3
+// at one dword column become four image words: transpose4x32, each word then rotated left by
+// kFoldImageRot bits.  The nibble of bit position j = 4 i + k (bit r = row r's bit j) so sits in
+// image word k at bits (4 i + kFoldImageRot .. + 3) mod 32: the even nibbles of a word, masked in
+// place, are byte offsets of 8-byte table entries (no shift), the odd ones after one shift by 4.
+constexpr int kFoldImageRot = 3;
+PIR_HD uint32_t fold_image_rotl(uint32_t w, int s) { return (w << s) | (w >> (32 - s)); }
+// rows -> image words, in place
+PIR_HD void fold_image4(uint32_t (&x)[4]) {
+  transpose4x32(x);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) x[k] = fold_image_rotl(x[k], kFoldImageRot);
+}
+// image words -> rows, in place (the rotation undone, then the transpose, its own inverse)
+PIR_HD void fold_image4_rows(uint32_t (&x)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) x[k] = fold_image_rotl(x[k], 32 - kFoldImageRot);
+  transpose4x32(x);
+}
+// the nibble of bit position j (0 .. 31) in the image words w
+PIR_HD uint32_t fold_image_nibble(const uint32_t (&w)[4], int j) {
+  return (fold_image_rotl(w[j & 3], 32 - kFoldImageRot) >> (4 * (j >> 2))) & 0xfu;
+}
+
 // 8 rows x 32 bits -> 32 bytes: afterwards byte i of x[k] holds bit (8i + k) of the original
 // rows, row r in bit r (four independent 8 x 8 transposes, one per byte column)
 PIR_HD void transpose8x32(uint32_t (&x)[8]) {

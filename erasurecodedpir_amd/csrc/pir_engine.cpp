@@ -351,6 +351,10 @@ int answer_batch_core(pir_engine* e, const uint8_t* d_raw, int nk, int log_parts
   if (int rc = ensure_batched(e, pl, FB, nk, G, queue && e->stream_narrow)) return rc;
   const size_t out_bytes = (size_t)c.num_rounds * c.record_bytes;
   const int last = pl.nstages - 1;
+  // the fold image of the rows from row0, for the full-width k_scan_t passes (built here, on s,
+  // ahead of the fork, where the rule says so: fold_image_for)
+  const uint8_t* d_img = nullptr;
+  if (int rc = fold_image_at(e, sh_full, row0, s, &d_img)) return rc;
   hipEvent_t* ev = queue ? e->ev : nullptr;
   if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
   HIP_TRY(hipEventRecord(e->ev_fork, s));
@@ -395,7 +399,7 @@ int answer_batch_core(pir_engine* e, const uint8_t* d_raw, int nk, int log_parts
     HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_cb_ready[b], 0));
     // slots g >= ng hold stale shares: their rounds are computed and dropped
     HIP_TRY(pir::launch_scan(sh, e->d_shard + row0 * e->pitch, pl.nleaves, cb, e->d_slabs, false,
-                             e->aux));
+                             e->aux, sh.tfold ? d_img : nullptr));
     HIP_TRY(hipEventRecord(e->ev_cb_free[b], e->aux));
     hipStream_t rs = e->aux;
     if (tail_on_s) {
@@ -746,6 +750,11 @@ int pir_engine_create(const pir_engine_config* cfg, pir_engine_t** out) {
     if (wds && wds[0]) e->wdd_share = std::max(0, std::min(2, atoi(wds)));
     const char* wdg = getenv("PIR_WDD_G");
     if (wdg && wdg[0]) e->wdd_group = atoi(wdg) >= 8 ? 8 : (atoi(wdg) >= 4 ? 4 : 2);
+    // $PIR_FOLD_IMAGE / $PIR_FOLD_IMAGE_MAX_BYTES: the fold image (include/pir_engine.h)
+    const char* fi = getenv("PIR_FOLD_IMAGE");
+    if (fi && fi[0]) e->fold_image = std::max(0, std::min(2, atoi(fi)));
+    const char* fm = getenv("PIR_FOLD_IMAGE_MAX_BYTES");
+    if (fm && fm[0]) e->fold_image_max = strtoull(fm, nullptr, 10);
     const char* bk = getenv("PIR_BATCH_KLAST");
     if (bk) e->batch_k_last = std::max(1, std::min(12, atoi(bk)));
     const int tile = pir::fused_tile(c.num_rounds, e->pitch, e->rows, e->num_cus);
@@ -840,6 +849,9 @@ int pir_engine_reserve_queue(pir_engine_t* e, int num_keys) {
     const pir::TreePlan pl = batch_plan(e, c.log_num_partitions, (uint64_t)c.partition_index, G, &FB);
     rc = ensure_batched(e, pl, FB, num_keys, G, e->stream_narrow);
     if (!rc) rc = ensure_bparts(e, total);
+    // the fold image, where the queue's passes are k_scan_t's
+    bool km = false;
+    if (!rc) rc = fold_image_reserve(e, group_scan_shape(e, pl.nleaves, G, G, &km));
     if (rc) return rc;
   }
   if (!qp.tile) return PIR_OK;  // shapes k_query does not take allocate per answer

@@ -463,6 +463,8 @@ int pir_engine_reserve_group_queue(pir_engine_t* e, int num_keys) {
   int rc = e->d_slabs.reserve(slab);
   // a shared queue at the widest share row (rows x 8 bytes whatever $PIR_GQ_G says)
   if (!rc && e->nrp <= 4) rc = ensure_group_queue(e, e->rows, 8 / e->nrp);
+  if (!rc && e->nrp <= 4 && e->gq_share && !e->comm)
+    rc = fold_image_reserve(e, woodruff_group_shape(e, e->rows, 8 / e->nrp));
   // the host forms' staging: one group's vectors, the keys, the results; the device form's
   // staging of unaligned keys, for the longest key a queue of this engine has brought so far
   const size_t vp = ((size_t)e->rows + 15) & ~(size_t)15;

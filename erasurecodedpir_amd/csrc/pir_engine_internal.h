@@ -149,6 +149,17 @@ struct pir_engine : eng::StreamSet {
   bool allow_fused = true;  // $PIR_FUSED=0 forces the 2-kernel path (A/B diagnostics)
   bool allow_query = true;  // $PIR_QUERY=0: frontier + k_fused instead of k_query
   eng::DevBuf<> d_shard;
+  // The fold image (pir_kernels.h: launch_fold_image): the shard once more, in the nibble-index
+  // form k_scan_t looks up by.  shard_epoch counts the writes to d_shard (eng::ShardWrite);
+  // the image is valid only while image_epoch equals it.  A pass that wants the image and finds
+  // none notes the epoch in image_wanted; the next one that finds the same epoch builds it
+  // (eng::fold_image_for), so a shard rewritten between queries never pays a build
+  eng::DevBuf<> d_image;
+  uint64_t shard_epoch = 1, image_epoch = 0, image_wanted = 0;
+  int fold_image = 1;               // $PIR_FOLD_IMAGE: 0 never, 1 (default) by the rule above and where it fits, 2 required
+  uint64_t fold_image_max = ~0ull;  // $PIR_FOLD_IMAGE_MAX_BYTES
+  bool fold_image_noroom = false;   // this epoch's image did not fit: not tried again
+  bool fold_image_noted = false;    // "no room" was said once
   eng::DevBuf<> d_key_raw;          // max_batch keys
   eng::DevBuf<pir::DevKey> d_keys;  // max_batch parsed keys
   int max_batch = 0;
@@ -281,6 +292,47 @@ int exchange(pir_engine* e, const uint8_t* d_part, size_t bytes, uint8_t* d_gath
              uint8_t* d_result, hipStream_t s);
 // pir_engine_prof.cpp
 hipEvent_t* prof_slot(pir_engine* e, int fused, int chunks, bool queue);
+// pir_engine_shard.cpp: the fold image's life
+// Held, under the engine's lock, by every entry point that writes d_shard: when it goes (on
+// every way out: a failed write may have written part) the shard has a new epoch and the image
+// of the old one is dropped
+struct ShardWrite {
+  explicit ShardWrite(pir_engine* e) : e_(e) {}
+  ~ShardWrite() {
+    ++e_->shard_epoch;
+    e_->image_epoch = 0;
+    e_->fold_image_noroom = false;
+    e_->d_image.release();
+  }
+  ShardWrite(const ShardWrite&) = delete;
+  ShardWrite& operator=(const ShardWrite&) = delete;
+
+ private:
+  pir_engine* const e_;
+};
+// build the image of the current shard on s now (the memory rule applies).  PIR_OK also when it
+// was left out for want of room in mode 1 (said once through last_error); mode 2 fails then
+int fold_image_build(pir_engine* e, hipStream_t s);
+// the image for a k_scan_t pass enqueued on s (or on a stream ordered after s): *img = the valid
+// image, else nullptr -- after building it here where the rule says so (struct pir_engine)
+int fold_image_for(pir_engine* e, hipStream_t s, const uint8_t** img);
+// the image at the engine rows [row0, ..) for a scan of shape sh, nullptr where the pass reads rows
+inline int fold_image_at(pir_engine* e, const pir::ScanShape& sh, uint64_t row0, hipStream_t s,
+                         const uint8_t** img) {
+  *img = nullptr;
+  if (!e->fold_image || !sh.tfold || row0 % 4 != 0) return PIR_OK;
+  if (int rc = fold_image_for(e, s, img)) return rc;
+  if (*img) *img += row0 * e->pitch;
+  return PIR_OK;
+}
+// a reserve call's part: the image now, where queues of shape sh will want it (so that none of
+// them allocates)
+inline int fold_image_reserve(pir_engine* e, const pir::ScanShape& sh) {
+  if (!e->fold_image || !sh.tfold) return PIR_OK;
+  if (int rc = fold_image_build(e, e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return PIR_OK;
+}
 // pir_engine_shamir.cpp
 int check_rows(const pir_engine* e, uint64_t row0, uint64_t nrows);
 int answer_coefs_locked(pir_engine* e, const uint8_t* src, uint64_t pitch, uint64_t row0,
@@ -324,12 +376,15 @@ int answer_group_queue(pir_engine* e, int nk, int G, int path, uint64_t row0, ui
     HIP_TRY(hipEventRecord(ev[EV_START], s));
   }
   const pir::ScanShape sh = woodruff_group_shape(e, nrec, G);
+  const uint8_t* d_img = nullptr;  // the fold image of the rows from row0 (k_scan_t passes)
+  if (int rc = fold_image_at(e, sh, row0, s, &d_img)) return rc;
   if (ev) HIP_TRY(hipEventRecord(ev[EV_SCAN_B], s));
   const int ngroups = (nk + G - 1) / G;
   for (int q0 = 0, j = 0, ng = 0; q0 < nk; q0 += ng, ++j) {
     ng = nk / ngroups + (j < nk % ngroups ? 1 : 0);
     HIP_TRY(write(q0, ng, e->d_cb, s));
-    HIP_TRY(pir::launch_scan(sh, e->d_shard + row0 * e->pitch, nrec, e->d_cb, e->d_slabs, false, s));
+    HIP_TRY(pir::launch_scan(sh, e->d_shard + row0 * e->pitch, nrec, e->d_cb, e->d_slabs, false, s,
+                             d_img));
     if (ev && q0 + ng >= nk) HIP_TRY(hipEventRecord(ev[EV_SCAN_E], s));
     uint8_t* dst = d_result + (size_t)q0 * out_bytes;
     if (e->nrp == c.num_rounds && ng * e->nrp == sh.nq) {

@@ -437,6 +437,7 @@ int pir_engine_encode_hermite_dev(pir_engine_t* e, const uint8_t* d_files, uint6
   if (d_files && file_pitch < file_bytes) return fail(PIR_EINVAL, "file_pitch < file_bytes");
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  ShardWrite sw(e);
   const uint64_t N = e->rows / 2;
   HIP_TRY(pir::launch_encode_hermite(d_files, file_pitch, num_files, file_bytes, k,
                                      party ? party : e->cfg.party_index,

@@ -161,7 +161,66 @@ uint64_t chunk_rows_for(uint64_t bytes_per_row) {
 
 }  // namespace
 
+int eng::fold_image_build(pir_engine* e, hipStream_t s) {
+  if (e->image_epoch == e->shard_epoch) return PIR_OK;
+  const size_t bytes = (size_t)((e->rows + 3) / 4 * 4) * e->pitch;
+  if (e->d_image.cap < bytes) {
+    // room: under the cap, and a sixteenth of the device's memory stays free afterwards
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > e->fold_image_max || free_b < bytes || free_b - bytes < total_b / 16) {
+      e->fold_image_noroom = true;
+      if (e->fold_image == 2)
+        return fail(PIR_ENOMEM, "fold image: no room for %zu bytes (free %zu of %zu, cap %llu)", bytes,
+                    free_b, total_b, (unsigned long long)e->fold_image_max);
+      if (!e->fold_image_noted)
+        (void)fail(PIR_OK, "fold image left out: no room for %zu bytes (free %zu of %zu, cap %llu)",
+                   bytes, free_b, total_b, (unsigned long long)e->fold_image_max);
+      e->fold_image_noted = true;
+      return PIR_OK;
+    }
+    if (e->d_image.reserve(bytes)) return fail(PIR_ENOMEM, "fold image: hipMalloc of %zu bytes", bytes);
+  }
+  HIP_TRY(pir::launch_fold_image(e->d_shard, e->rows, e->pitch, e->d_image, s));
+  e->image_epoch = e->shard_epoch;
+  return PIR_OK;
+}
+
+int eng::fold_image_for(pir_engine* e, hipStream_t s, const uint8_t** img) {
+  *img = nullptr;
+  if (!e->fold_image) return PIR_OK;
+  // (mode 2 asks again every time, and fails every time, where the image does not fit)
+  if (e->image_epoch != e->shard_epoch && (!e->fold_image_noroom || e->fold_image == 2)) {
+    if (e->fold_image == 2 || e->image_wanted == e->shard_epoch) {
+      if (int rc = fold_image_build(e, s)) return rc;
+    } else {
+      e->image_wanted = e->shard_epoch;  // wanted once: the next pass over this shard builds it
+    }
+  }
+  if (e->image_epoch == e->shard_epoch) *img = e->d_image;
+  return PIR_OK;
+}
+
 extern "C" {
+
+int pir_engine_fold_image(pir_engine_t* e, int op, uint64_t* bytes_held) {
+  if (!e || op < PIR_FOLD_IMAGE_REPORT || op > PIR_FOLD_IMAGE_DROP) return fail(PIR_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  int rc = PIR_OK;
+  if (op == PIR_FOLD_IMAGE_DROP) {
+    e->image_epoch = 0;
+    e->image_wanted = 0;
+    e->d_image.release();
+  } else if (op == PIR_FOLD_IMAGE_BUILD) {
+    if (!e->fold_image) return fail(PIR_EINVAL, "the fold image is switched off (PIR_FOLD_IMAGE=0)");
+    e->fold_image_noroom = false;
+    rc = fold_image_build(e, e->stream);
+    if (!rc) HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  if (bytes_held) *bytes_held = e->image_epoch == e->shard_epoch ? e->d_image.cap : 0;
+  return rc;
+}
 
 int pir_engine_set_shard(pir_engine_t* e, const uint8_t* host, uint64_t row0, uint64_t nrows,
                          uint64_t src_pitch) {
@@ -173,6 +232,7 @@ int pir_engine_set_shard(pir_engine_t* e, const uint8_t* host, uint64_t row0, ui
   if (src_pitch < e->cfg.record_bytes) return fail(PIR_EINVAL, "src_pitch < record_bytes");
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  ShardWrite sw(e);
   // 2-D copy writes record_bytes per row; the pad bytes stay zero from the create memset
   HIP_TRY(hipMemcpy2DAsync(e->d_shard + row0 * e->pitch, e->pitch, host, src_pitch,
                            e->cfg.record_bytes, nrows, hipMemcpyHostToDevice, e->stream));
@@ -186,6 +246,7 @@ int pir_engine_set_shard_rows(pir_engine_t* e, const uint8_t* const* rows, uint6
   if (row0 + nrows > e->rows) return fail(PIR_EINVAL, "rows beyond shard");
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  ShardWrite sw(e);
   const uint32_t efs = e->cfg.record_bytes;
   const uint64_t m = chunk_rows_for(efs);
   return staged_h2d(
@@ -250,6 +311,7 @@ int pir_engine_fill_shard_random(pir_engine_t* e, uint64_t seed) {
   if (!e) return fail(PIR_EINVAL, "null engine");
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  ShardWrite sw(e);
   const uint64_t row0 = (uint64_t)e->cfg.partition_index * e->rows;
   HIP_TRY(pir::launch_fill_shard(e->d_shard, e->rows, e->pitch, e->cfg.record_bytes, row0, seed,
                                  e->stream));
@@ -269,6 +331,7 @@ static int encode_across_dev(pir_engine_t* e, const uint8_t* d_files, uint64_t f
                 k, (unsigned long long)encdb, e->cfg.log_num_records);
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  ShardWrite sw(e);
   const uint64_t row0 = (uint64_t)e->cfg.partition_index * e->rows;
   // CheckMAC: the 257 distinct synthetic payloads (bytes v, and file 1's ramp as entry 256) are
   // materialised once, tagged by k_hmac_sha256_files, and the encode reads the 257 x 32 table
@@ -319,6 +382,7 @@ int pir_engine_encode_across_rows(pir_engine_t* e, const uint8_t* const* files, 
                 k, (unsigned long long)encdb, e->cfg.log_num_records);
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  ShardWrite sw(e);
   const uint32_t efs = e->cfg.record_bytes;
   const uint64_t prow0 = (uint64_t)e->cfg.partition_index * e->rows;
   // chunk c = this engine's rows [c m, (c + 1) m): its k source files per row staged as k blocks
@@ -370,6 +434,7 @@ int pir_engine_encode_within_rows(pir_engine_t* e, const uint8_t* const* files, 
                 e->cfg.record_bytes);
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  ShardWrite sw(e);
   const uint64_t prow0 = (uint64_t)e->cfg.partition_index * e->rows;
   const uint32_t fb = std::max<uint32_t>(file_bytes, 1);
   // chunk c = this engine's rows [c m, (c + 1) m) = files prow0 + c m + r (one file per row)
@@ -425,6 +490,7 @@ int pir_engine_encode_within_dev(pir_engine_t* e, const uint8_t* d_files, uint64
                 e->cfg.log_num_records);
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  ShardWrite sw(e);
   const uint64_t row0 = (uint64_t)e->cfg.partition_index * e->rows;
   HIP_TRY(pir::launch_encode_within(d_files, file_pitch, num_files, file_bytes, k,
                                     party ? party : e->cfg.party_index, e->d_shard, e->rows,

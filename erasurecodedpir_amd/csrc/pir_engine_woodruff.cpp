@@ -374,6 +374,8 @@ int pir_engine_reserve_woodruff_queue(pir_engine_t* e, int num_keys) {
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
   int rc = ensure_woodruff_queue(e, M, num_keys, e->rows);
+  if (const int G = rc ? 0 : woodruff_group(e, num_keys))
+    rc = fold_image_reserve(e, woodruff_group_shape(e, e->rows, G));
   // the host form's staging
   if (!rc) rc = e->d_coef_stage.reserve((size_t)num_keys * M);
   if (!rc)

@@ -139,8 +139,15 @@ bool scan_t_enabled();
 // prefer: also 4-5 rounds of wider records (a batched group's key-major shares: packed leaf
 // stores, which the interleaved layout of the k_scan_uni forms does not allow)
 bool scan_t_shape(int nq, int nrp, uint32_t pitch, bool prefer = false);
+// d_image: the fold image of the same rows (launch_fold_image; the first row a multiple of 4 of
+// the image's rows, pitch % 16 == 0), read in place of d_shard
 hipError_t launch_scan_t(const ScanShape& sh, const uint8_t* d_shard, uint64_t nrec,
-                         const uint8_t* d_c, uint8_t* d_slabs, int acc, hipStream_t s);
+                         const uint8_t* d_c, uint8_t* d_slabs, int acc, hipStream_t s,
+                         const uint8_t* d_image = nullptr);
+// The fold image of rows [0, nrows) (pir_bits.h: fold_image4): round_up(nrows, 4) * pitch bytes,
+// block b of 4 rows at b * 4 * pitch, dword column c's 16 bytes at 16 c; rows past nrows zero
+hipError_t launch_fold_image(const uint8_t* d_shard, uint64_t nrows, uint32_t pitch,
+                             uint8_t* d_image, hipStream_t s);
 // k_scan_uni for 4-5 rounds at two dwords per lane: four-Russians folds need 168 VGPRs, so one
 // 768-thread workgroup per CU (only where the caller leaves the CU to the scan: blocks_per_cu 0)
 constexpr int kScanM4rThreads = 768;
@@ -149,8 +156,10 @@ constexpr int kScanM4rThreads = 768;
 ScanShape make_scan_shape(uint64_t nrec, uint32_t pitch, int nq, int num_cus, int blocks_per_cu = 0,
                           bool prefer_t = false);
 // accumulate: XOR into the slabs instead of overwriting them (chunked scans of one answer)
+// d_image: the fold image at d_shard's rows (launch_scan_t), used where the shape is tfold
 hipError_t launch_scan(const ScanShape& sh, const uint8_t* d_shard, uint64_t nrec,
-                       const uint8_t* d_c, uint8_t* d_slabs, bool accumulate, hipStream_t s);
+                       const uint8_t* d_c, uint8_t* d_slabs, bool accumulate, hipStream_t s,
+                       const uint8_t* d_image = nullptr);
 // Fused leaf stage + scan (one persistent workgroup per CU).  fused_tile() = leaves per tile
 // (0: not supported for this shape -> 2-kernel path); plan with make_plan(.., fused_k(tile)).
 int fused_tile(int nq, uint32_t pitch, uint64_t nleaves, int num_cus);

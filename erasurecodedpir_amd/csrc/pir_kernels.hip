@@ -3499,7 +3499,8 @@ static hipError_t scan_nq(const ScanShape& sh, const uint8_t* d_shard, uint64_t 
 }
 
 hipError_t launch_scan(const ScanShape& sh, const uint8_t* d_shard, uint64_t nrec,
-                       const uint8_t* d_c, uint8_t* d_slabs, bool accumulate, hipStream_t s) {
+                       const uint8_t* d_c, uint8_t* d_slabs, bool accumulate, hipStream_t s,
+                       const uint8_t* d_image) {
   // bit 1: the waves of a k_scan_uni / k_scan_t workgroup claim row chunks instead of folding a
   // fixed range each (round 6: Hollanti 5 rounds 3.60 -> 3.12-3.30 ms, 3 rounds -1.5 %,
   // profiles/r06/r6w_*, r6x_*; $PIR_SCAN_DYN=0 restores the fixed ranges)
@@ -3508,7 +3509,10 @@ hipError_t launch_scan(const ScanShape& sh, const uint8_t* d_shard, uint64_t nre
   if (sh.tfold) {
     // k_scan_t addresses a workgroup's rows through one buffer resource when they claim chunks
     const bool wg_fits = (nrec / sh.grid.x + 1) * (uint64_t)sh.pitch < (1ull << 31);
-    return launch_scan_t(sh, d_shard, nrec, d_c, d_slabs, wg_fits ? acc : (acc & 1), s);
+    // the image's blocks of 4 rows: up to 3 rows more per wave or workgroup
+    const bool img_fits = (nrec / sh.grid.x + 5) * (uint64_t)sh.pitch < (1ull << 31);
+    return launch_scan_t(sh, d_shard, nrec, d_c, d_slabs, wg_fits ? acc : (acc & 1), s,
+                         img_fits ? d_image : nullptr);
   }
   switch (sh.nq) {
     case 1: return scan_nq<1>(sh, d_shard, nrec, d_c, d_slabs, acc, s);

@@ -31,6 +31,8 @@
 // and pir_woodruff_q.hip.  Here are what is k_scan_t's own: the row loads, the coefficient gather
 // (record- or key-major), the chunk claims, red[] and the slabs, and the launch.
 #include <stdlib.h>
+
+#include <algorithm>
 #include "pir_kernels.h"
 #include "pir_seg_walk.h"
 
@@ -38,7 +40,34 @@ namespace pir {
 
 constexpr int kScanTWaves = kScanTThreads / 64;
 
-template <int NQ, int NRP>
+// The fold image of rows [0, nrows) of `shard` (pir_bits.h: fold_image4): lane = one dword column
+// of one block of 4 rows, 4 dword loads and one 16-byte store at block * 4 * pitch + 16 * column;
+// the rows past nrows of the last block count as zero.  Grid x = blocks, y = column groups of 256
+__global__ __launch_bounds__(256) void k_fold_image(const uint8_t* __restrict__ shard,
+                                                    uint64_t nrows, uint32_t pitch,
+                                                    uint8_t* __restrict__ image) {
+  const uint32_t col = blockIdx.y * 256 + threadIdx.x;
+  if (col >= pitch / 4) return;
+  const uint64_t blocks = (nrows + 3) / 4;
+  for (uint64_t blk = blockIdx.x; blk < blocks; blk += gridDim.x) {
+    uint32_t x[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint64_t row = 4 * blk + r;
+      x[r] = row < nrows ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(
+                               shard + row * pitch) + col)
+                         : 0u;
+    }
+    fold_image4(x);
+    *reinterpret_cast<uint4*>(image + blk * 4 * pitch + 16ull * col) =
+        make_uint4(x[0], x[1], x[2], x[3]);
+  }
+}
+
+// IMG: `shard` is the fold image of the rows (k_fold_image), the first of them a multiple of 4 in
+// the image's row numbering: block loads of 16 bytes per lane, no transposes in the loop.  The
+// waves' (workgroups') row ranges start on multiples of 4
+template <int NQ, int NRP, bool IMG>
 __global__ __launch_bounds__(kScanTThreads) __attribute__((amdgpu_waves_per_eu(kScanTWavesPerEU)))
 void k_scan_t(const uint8_t* __restrict__ shard, uint64_t nrec, uint32_t pitch, uint32_t cpr,
               const uint8_t* __restrict__ c, uint8_t* __restrict__ slabs, int accumulate,
@@ -64,8 +93,13 @@ void k_scan_t(const uint8_t* __restrict__ shard, uint64_t nrec, uint32_t pitch, 
   const uint32_t chunk = blockIdx.y * kColGroupLanes + lane;
   const bool active = chunk < cpr;
   // the wave's rows, or (dyn) the workgroup's
-  const uint64_t r0 = dyn ? (uint64_t)blockIdx.x * kScanTWaves * nrec / nwaves : wave * nrec / nwaves;
-  const uint64_t r1 = dyn ? ((uint64_t)blockIdx.x + 1) * kScanTWaves * nrec / nwaves : (wave + 1) * nrec / nwaves;
+  // (IMG: every boundary but the last rounded down to a block of 4 rows)
+  auto bound = [&](uint64_t i) __attribute__((always_inline)) {
+    const uint64_t r = i * nrec / nwaves;
+    return IMG && i < nwaves ? r & ~(uint64_t)3 : r;
+  };
+  const uint64_t r0 = bound(dyn ? (uint64_t)blockIdx.x * kScanTWaves : wave);
+  const uint64_t r1 = bound(dyn ? ((uint64_t)blockIdx.x + 1) * kScanTWaves : wave + 1);
   if (dyn) {
     if (threadIdx.x == 0) next_chunk = 0;
     __syncthreads();
@@ -74,11 +108,20 @@ void k_scan_t(const uint8_t* __restrict__ shard, uint64_t nrec, uint32_t pitch, 
   uint32_t Zt[32][WD] = {};  // a wave without rows adds nothing
   if (r1 > r0) {
     const uint32_t nrows = (uint32_t)(r1 - r0);
+    // (IMG: whole blocks of 4 rows, block b of the wave's at b * 4 * pitch, the lane's 16 bytes
+    // at 16 * chunk)
+    const uint32_t nspan = IMG ? (nrows + 3u) & ~3u : nrows;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(shard + r0 * pitch), (short)0, (int)(nrows * pitch), kBufRsrcWord3);
-    const uint32_t voff = (active ? chunk : 0u) * 4u;  // inactive lanes: the row's first dword
+        (void*)(shard + r0 * pitch), (short)0, (int)(nspan * pitch), kBufRsrcWord3);
+    const uint32_t voff = (active ? chunk : 0u) * (IMG ? 16u : 4u);  // inactive lanes: column 0
     auto load = [&](uint32_t rel) __attribute__((always_inline)) {
-      return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, voff, rel * pitch, 2);
+      if constexpr (IMG) {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, rel * 4u * pitch, 2);
+        return make_uint4(v.x, v.y, v.z, v.w);
+      } else {
+        return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, voff, rel * pitch, 2);
+      }
     };
     // lane l: the coefficient words of row rb + l (zero past the wave's rows); key-major
     // coefficients (ckey bytes per key) are gathered key by key: one ckey-byte load per key,
@@ -113,7 +156,7 @@ void k_scan_t(const uint8_t* __restrict__ shard, uint64_t nrec, uint32_t pitch, 
         v = __hip_atomic_fetch_add(&next_chunk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       return (uint32_t)__builtin_amdgcn_readfirstlane(v);
     };
-    fr_walk<WD>(
+    fr_walk<WD, IMG>(
         nrows, load, coefs64, dyn ? claim() : 0u,
         [&](uint32_t cur) __attribute__((always_inline)) {
           return dyn ? (cur < nch ? claim() : nch) : cur + 1;
@@ -153,21 +196,37 @@ bool scan_t_shape(int nq, int nrp, uint32_t pitch, bool prefer) {
 
 template <int NQ, int NRP>
 static hipError_t scan_t_launch(const ScanShape& sh, const uint8_t* d_shard, uint64_t nrec,
-                                const uint8_t* d_c, uint8_t* d_slabs, int acc, hipStream_t s) {
+                                const uint8_t* d_c, uint8_t* d_slabs, int acc, hipStream_t s,
+                                const uint8_t* d_image) {
   if (sh.ckey != 0 && (sh.ckey > 4 || NRP % sh.ckey != 0)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_scan_t<NQ, NRP>), sh.grid, dim3(kScanTThreads), 0, s, d_shard, nrec,
-                     sh.pitch, sh.cpr, d_c, d_slabs, acc, sh.ckey, sh.ckoff);
+  if (d_image)
+    hipLaunchKernelGGL((k_scan_t<NQ, NRP, true>), sh.grid, dim3(kScanTThreads), 0, s, d_image,
+                       nrec, sh.pitch, sh.cpr, d_c, d_slabs, acc, sh.ckey, sh.ckoff);
+  else
+    hipLaunchKernelGGL((k_scan_t<NQ, NRP, false>), sh.grid, dim3(kScanTThreads), 0, s, d_shard,
+                       nrec, sh.pitch, sh.cpr, d_c, d_slabs, acc, sh.ckey, sh.ckoff);
   return hipGetLastError();
 }
 
 hipError_t launch_scan_t(const ScanShape& sh, const uint8_t* d_shard, uint64_t nrec,
-                         const uint8_t* d_c, uint8_t* d_slabs, int acc, hipStream_t s) {
+                         const uint8_t* d_c, uint8_t* d_slabs, int acc, hipStream_t s,
+                         const uint8_t* d_image) {
   if (sh.threads != kScanTThreads || sh.vec != 1 || !sh.uniform) return hipErrorInvalidValue;
+  if (d_image && (sh.pitch % 16 != 0 || ((uintptr_t)d_image & 15) != 0)) return hipErrorInvalidValue;
 #define PIR_ST(NQ, NRP) \
-  if (sh.nq == NQ && sh.nrp == NRP) return scan_t_launch<NQ, NRP>(sh, d_shard, nrec, d_c, d_slabs, acc, s)
+  if (sh.nq == NQ && sh.nrp == NRP) return scan_t_launch<NQ, NRP>(sh, d_shard, nrec, d_c, d_slabs, acc, s, d_image)
   PIR_ST(4, 4); PIR_ST(4, 8); PIR_ST(5, 8); PIR_ST(6, 8); PIR_ST(7, 8); PIR_ST(8, 8);
 #undef PIR_ST
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_fold_image(const uint8_t* d_shard, uint64_t nrows, uint32_t pitch,
+                             uint8_t* d_image, hipStream_t s) {
+  if (pitch % 16 != 0 || nrows == 0) return hipErrorInvalidValue;
+  const uint64_t blocks = (nrows + 3) / 4;
+  const dim3 grid((unsigned)std::min<uint64_t>(blocks, 1u << 20), (pitch / 4 + 255) / 256);
+  hipLaunchKernelGGL(k_fold_image, grid, dim3(256), 0, s, d_shard, nrows, pitch, d_image);
+  return hipGetLastError();
 }
 
 }  // namespace pir

@@ -79,7 +79,11 @@ __device__ __forceinline__ void fr_build_tables(const uint2& cw, uint32_t q2, ui
 //               from a workgroup's counter).  The rows and coefficient words loaded ahead come
 //               from the next chunk past the current one's end
 //   tw          the wave's own FrTab<WD>::kWords dwords of LDS
-template <int WD, class Load, class Coefs, class Next>
+// IMG: the rows come from a fold image (pir_bits.h: fold_image4; k_fold_image builds it).  The
+// wave's first row is a multiple of 4, load(blk) returns the four image words of the rows 4 blk ..
+// 4 blk + 3 -- asked for only with 4 blk < nrows, and for block 0 in place of the blocks past the
+// last -- and the two transposes per group, with the shift of the even nibbles, are not done
+template <int WD, bool IMG = false, class Load, class Coefs, class Next>
 __device__ __forceinline__ void fr_walk(uint32_t nrows, Load&& load, Coefs&& coefs, uint32_t first,
                                         Next&& next, uint32_t lane, uint32_t* tw,
                                         uint32_t (&Zt)[32][WD]) {
@@ -97,14 +101,34 @@ __device__ __forceinline__ void fr_walk(uint32_t nrows, Load&& load, Coefs&& coe
     return load(rel < nrows ? rel : 0u);
   };
   uint32_t x[16];
+  // rows rel .. rel + n - 1 into x[u0 ..] (IMG: rel a multiple of 4 or >= nrows, n of 4)
+  auto fetch = [&](int u0, int n, uint32_t rel) __attribute__((always_inline)) {
+    if constexpr (IMG) {
 #pragma unroll
-  for (int u = 0; u < 16; ++u) x[u] = load_rel(cur * 64 + (uint32_t)u);
+      for (int u = 0; u < n; u += 4) {
+        const uint4 b = load(rel + (uint32_t)u < nrows ? (rel + (uint32_t)u) / 4 : 0u);
+        x[u0 + u] = b.x, x[u0 + u + 1] = b.y, x[u0 + u + 2] = b.z, x[u0 + u + 3] = b.w;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < n; ++u) x[u0 + u] = load_rel(rel + (uint32_t)u);
+    }
+  };
+  fetch(0, 16, cur * 64);
   uint2 cw = coefs(cur * 64);  // zero by itself when the wave has no chunk (cur >= nch)
   for (; cur < nch;) {
     const uint32_t rb = cur * 64;
     const uint2 cwn = nxt < nch ? coefs(nxt * 64) : make_uint2(0, 0);  // next chunk's, in flight
     const uint32_t nb = nrows - rb < 64 ? nrows - rb : 64;
-    fr_build_tables<WD>(cw, q2, q3, lane, tw);
+    if constexpr (IMG) {
+      // the 16-byte loads take aligned register quads: the two masks are made again per chunk
+      // (from a copy of the lane number the compiler cannot see through) and not kept
+      uint32_t l = lane;
+      asm volatile("" : "+v"(l));
+      fr_build_tables<WD>(cw, 0u - (l & 1u), 0u - ((l >> 1) & 1u), l, tw);
+    } else {
+      fr_build_tables<WD>(cw, q2, q3, lane, tw);
+    }
     for (uint32_t j0 = 0; j0 < nb; j0 += 16) {
       const char* const tj = reinterpret_cast<const char*>(tw) + j0 / 4 * kTabBytes;  // rows j0 ..
       // the 16 rows loaded ahead: this chunk's next, or past its end the next chunk's first
@@ -116,8 +140,10 @@ __device__ __forceinline__ void fr_walk(uint32_t nrows, Load&& load, Coefs&& coe
         // rows' table
         uint32_t (&L)[4] = *reinterpret_cast<uint32_t(*)[4]>(&x[8 * g]);  // in place
         uint32_t (&H)[4] = *reinterpret_cast<uint32_t(*)[4]>(&x[8 * g + 4]);
-        transpose4x32(L);
-        transpose4x32(H);
+        if constexpr (!IMG) {
+          transpose4x32(L);
+          transpose4x32(H);
+        }
         // 8 steps of 4 bit positions (8 lookups), software-pipelined: step s + 1's reads are
         // issued before step s's XORs (16 reads in flight; left alone the scheduler waits on
         // each read).  Step s takes the even (s even) or odd nibbles of the words L[s / 2],
@@ -128,8 +154,16 @@ __device__ __forceinline__ void fr_walk(uint32_t nrows, Load&& load, Coefs&& coe
         const char* const tg = tj + g * (2 * kTabBytes);
         Ent ta[8], tb[8];
         auto issue = [&](Ent (&t)[8], int s) __attribute__((always_inline)) {
-          uint32_t lo = (s & 1) ? L[s >> 1] >> (4 - ESH) : L[s >> 1] << ESH;
-          uint32_t hi = (s & 1) ? H[s >> 1] >> (4 - ESH) : H[s >> 1] << ESH;
+          uint32_t lo, hi;
+          if constexpr (IMG) {  // image words: rotated left by kFoldImageRot already
+            constexpr int R = kFoldImageRot - ESH;
+            static_assert(R >= 0, "the image's rotation covers the entry size");
+            lo = __builtin_rotateright32(L[s >> 1], (s & 1) ? R + 4 : R);
+            hi = __builtin_rotateright32(H[s >> 1], (s & 1) ? R + 4 : R);
+          } else {
+            lo = (s & 1) ? L[s >> 1] >> (4 - ESH) : L[s >> 1] << ESH;
+            hi = (s & 1) ? H[s >> 1] >> (4 - ESH) : H[s >> 1] << ESH;
+          }
           lo &= 0x0f0f0f0fu << ESH;
           hi &= 0x0f0f0f0fu << ESH;
           asm volatile("" : "+v"(lo), "+v"(hi));
@@ -169,8 +203,7 @@ __device__ __forceinline__ void fr_walk(uint32_t nrows, Load&& load, Coefs&& coe
         issue(tb, 7);
         fold(ta, 6);
         fold(tb, 7);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) x[8 * g + r] = load_rel(ahead + 8 * g + r);
+        fetch(8 * g, 8, ahead + 8 * g);
         __builtin_amdgcn_sched_barrier(0);  // one group at a time (register pressure)
       }
     }

@@ -592,6 +592,15 @@ class Engine:
         so no device synchronisation, inside later answer_stream_dev calls)."""
         check(self._lib.pir_engine_reserve_queue(self._h, num_keys), "reserve_queue")
 
+    def fold_image(self, op="report"):
+        """The fold image (a bit-transposed second copy of the shard for the shared-queue scan;
+        $PIR_FOLD_IMAGE, include/pir_engine.h): op = "report", "build" (now) or "drop".  Returns
+        the bytes of a valid image held afterwards (0: none)."""
+        held = ctypes.c_uint64(0)
+        check(self._lib.pir_engine_fold_image(self._h, {"report": 0, "build": 1, "drop": 2}[op],
+                                              ctypes.byref(held)), "fold_image")
+        return held.value
+
     def answer_stream(self, keys):
         """Host form of answer_stream_dev: [num_keys, num_rounds, record_bytes]."""
         keys = [bytes(k) for k in keys]

@@ -424,6 +424,19 @@ int pir_engine_answer_stream_dev(pir_engine_t *e, const uint8_t *d_keys, int num
  * the batched node buffers, the parsed keys and, with a communicator, the partition buffers):
  * the reference has no counterpart (its buffers are host mallocs per call, server.cpp:108-114). */
 int pir_engine_reserve_queue(pir_engine_t *e, int num_keys);
+/* The fold image: a second copy of the shard (round_up(rows, 4) x padded record bytes of device
+ * memory), bit-transposed once so that the shared-queue scan (k_scan_t) need not transpose it in
+ * every pass.  Answers are the same with and without it.  $PIR_FOLD_IMAGE, read at engine
+ * creation: 0 never; unset or 1 builds it in pir_engine_reserve_queue for a queue that shares
+ * passes, and in a shared queue or batch that finds the shard unchanged since the previous one
+ * wanted it (a shard rewritten between queries never pays a build), and only while a sixteenth
+ * of the device's memory stays free afterwards -- else the answers run without it and
+ * pir_engine_last_error says so once; 2 builds it wherever a pass can use it and fails where it
+ * does not fit.  $PIR_FOLD_IMAGE_MAX_BYTES caps its size.  Every write to the shard drops it.
+ * op: report only, build now (synchronous; an error with $PIR_FOLD_IMAGE=0), or drop;
+ * *bytes_held (may be NULL) = the bytes of a valid image afterwards, 0 without one. */
+enum { PIR_FOLD_IMAGE_REPORT = 0, PIR_FOLD_IMAGE_BUILD = 1, PIR_FOLD_IMAGE_DROP = 2 };
+int pir_engine_fold_image(pir_engine_t *e, int op, uint64_t *bytes_held);
 /* keys per shard pass: 0 = automatic (8 / nrp), else a power of two <= 16 / nrp, where nrp =
  * num_rounds rounded up to a power of two.  Default from $PIR_BATCH_G. */
 int pir_engine_set_batch_group(pir_engine_t *e, int keys_per_pass);
