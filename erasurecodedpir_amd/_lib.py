@@ -92,6 +92,13 @@ PROTOTYPES = {
     "pir_engine_encode_within_dev": (_I, [_P, _P, _U64, _U64, ctypes.c_uint32, _I, _I]),
     "pir_engine_get_shard_row": (_I, [_P, _U64, _P]),
     "pir_engine_get_shard": (_I, [_P, _U64, _U64, _P]),
+    "pir_engine_update_rows_dev": (_I, [_P, _P, _I, _P, _U64, _P]),
+    "pir_engine_update_rows": (_I, [_P, _P, _I, _P, _U64]),
+    "pir_engine_update_across_dev": (_I, [_P, _P, _I, _P, _U64, _U64, _I, _P]),
+    "pir_engine_update_across": (_I, [_P, _P, _I, _P, _U64, _U64, _I]),
+    "pir_engine_update_within_dev": (_I, [_P, _P, _I, _P, _U64, _U64, _U32, _I, _I, _I, _P]),
+    "pir_engine_update_within": (_I, [_P, _P, _I, _P, _U64, _U64, _U32, _I, _I, _I]),
+    "pir_engine_update_across_mac_dev": (_I, [_P, _P, _I, _P, _P, _U64, _U64, _I, _P, _P]),
     "pir_engine_answer": (_I, [_P, _P, _P]),
     "pir_engine_answer_slice": (_I, [_P, _P, _I, _I, _P]),
     "pir_engine_answer_slices": (_I, [_P, _P, _I, _P]),

@@ -123,11 +123,14 @@ struct StreamSet {
   // for the engine's own stream when the next answer comes on another one)
   hipEvent_t ev_ws = nullptr;
   hipStream_t ws_stream = nullptr;
+  // live updates: the copy that read the pinned term table h_upd[i] has completed (made on first
+  // use, pir_engine_update.cpp)
+  hipEvent_t ev_upd[2] = {};
   ~StreamSet() {
     for (hipEvent_t ev : ev_leaf)
       if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {ev_cb_ready[0], ev_cb_ready[1], ev_cb_free[0], ev_cb_free[1], ev_fork,
-                          ev_join, ev_ws})
+                          ev_join, ev_ws, ev_upd[0], ev_upd[1]})
       if (ev) (void)hipEventDestroy(ev);
     if (aux) (void)hipStreamDestroy(aux);
     if (stream) (void)hipStreamDestroy(stream);
@@ -160,6 +163,13 @@ struct pir_engine : eng::StreamSet {
   uint64_t fold_image_max = ~0ull;  // $PIR_FOLD_IMAGE_MAX_BYTES
   bool fold_image_noroom = false;   // this epoch's image did not fit: not tried again
   bool fold_image_noted = false;    // "no room" was said once
+  // live updates (pir_engine_update.cpp): the term table of a batch, in two pinned buffers taken
+  // in turn and on the device; the staged deltas of the host forms and the CheckMAC form, and
+  // that form's tags.  An update moves shard_epoch without a ShardWrite: a valid image is patched
+  // and follows (image_epoch), and image_wanted is carried to the new epoch
+  eng::PinnedBuf h_upd[2];
+  int upd_next = 0;
+  eng::DevBuf<> d_upd, d_upd_delta, d_upd_tags;
   eng::DevBuf<> d_key_raw;          // max_batch keys
   eng::DevBuf<pir::DevKey> d_keys;  // max_batch parsed keys
   int max_batch = 0;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pir_update_plan.h"
+
 namespace pir {
 
 constexpr int kMaxLevels = 40;  // PIR_MAX_LOG_RECORDS
@@ -148,6 +150,22 @@ hipError_t launch_scan_t(const ScanShape& sh, const uint8_t* d_shard, uint64_t n
 // block b of 4 rows at b * 4 * pitch, dword column c's 16 bytes at 16 c; rows past nrows zero
 hipError_t launch_fold_image(const uint8_t* d_shard, uint64_t nrows, uint32_t pitch,
                              uint8_t* d_image, hipStream_t s);
+// k_update_rows (pir_update.hip): the terms of a live update, sorted into nblocks 4-row blocks
+// (pir_update_plan.h: update_plan), XORed into the rows of d_shard -- term t: row ^= coef * bytes
+// [off, off + efs) of delta number `delta` (d_delta + delta * delta_pitch, any alignment), its
+// bytes at or past `limit` zero and not read -- and, with d_image, fold_image4 of every touched
+// block written over the image's (launch_fold_image's layout): the image stays exact
+hipError_t launch_update_rows(const UpdateBlock* d_blocks, uint32_t nblocks,
+                              const UpdateTerm* d_terms, const uint8_t* d_delta,
+                              uint64_t delta_pitch, uint32_t limit, uint8_t* d_shard,
+                              uint64_t nrows, uint32_t pitch, uint32_t efs, uint8_t* d_image,
+                              hipStream_t s);
+// d_out + i * (payload + 32) = the delta of CheckMAC record i: (d_old ^ d_new)[i * pitch ..] over
+// the payload, then tag i ^ tag num + i of d_tags (32 bytes each: the old payloads' tags, then the
+// new ones')
+hipError_t launch_update_mac_delta(const uint8_t* d_old, const uint8_t* d_new, uint64_t pitch,
+                                   const uint8_t* d_tags, uint64_t num, uint32_t payload,
+                                   uint8_t* d_out, hipStream_t s);
 // k_scan_uni for 4-5 rounds at two dwords per lane: four-Russians folds need 168 VGPRs, so one
 // 768-thread workgroup per CU (only where the caller leaves the CU to the scan: blocks_per_cu 0)
 constexpr int kScanM4rThreads = 768;

@@ -158,6 +158,99 @@ class Engine:
                                              out.ctypes.data_as(ctypes.c_void_p)), "get_shard")
         return out
 
+    # -- live updates ----------------------------------------------------------------------
+    # Changed records patched into the resident shard, and into a valid fold image, in place
+    # (include/pir_engine.h, "live record updates").  Every form takes DELTAS, old ^ new.
+    @staticmethod
+    def _index(index):
+        idx = np.ascontiguousarray(np.asarray(index, np.uint64).reshape(-1))
+        return idx, idx.ctypes.data_as(ctypes.c_void_p)
+
+    @staticmethod
+    def _deltas(deltas, num):
+        d = np.ascontiguousarray(np.asarray(deltas, np.uint8).reshape(num, -1)) if num \
+            else np.zeros((0, 1), np.uint8)
+        return d, d.ctypes.data_as(ctypes.c_void_p), d.shape[1]
+
+    def update_rows(self, rows, deltas):
+        """Engine row rows[i] ^= deltas[i] ((num, record_bytes) uint8)."""
+        idx, ip = self._index(rows)
+        d, dp, pitch = self._deltas(deltas, idx.size)
+        check(self._lib.pir_engine_update_rows(self._h, ip, idx.size, dp, pitch), "update_rows")
+
+    def update_across(self, file_index, deltas, num_files, k):
+        """Files file_index[i] of an across-encoded database (encode_across(num_files, k, files))
+        changed by deltas[i] = old ^ new ((num, record_bytes) uint8): afterwards the shard is what
+        encode_across gives from the new files."""
+        idx, ip = self._index(file_index)
+        d, dp, pitch = self._deltas(deltas, idx.size)
+        check(self._lib.pir_engine_update_across(self._h, ip, idx.size, dp, pitch, num_files, k),
+              "update_across")
+
+    def update_within(self, file_index, deltas, num_files, file_bytes, k, party=0, hermite=False):
+        """Files file_index[i] of a within-encoded database (encode_within) changed by deltas[i] =
+        old ^ new ((num, file_bytes) uint8); hermite: a Shamir engine, whose Hermite rows
+        (encode_hermite) follow too.  party as for encode_within."""
+        idx, ip = self._index(file_index)
+        d, dp, pitch = self._deltas(deltas, idx.size)
+        check(self._lib.pir_engine_update_within(self._h, ip, idx.size, dp, pitch, num_files,
+                                                 file_bytes, k, party, int(bool(hermite))),
+              "update_within")
+
+    def update_across_mac(self, file_index, old, new, num_files, k, key):
+        """update_across for a CheckMAC setup: old / new are the files' PAYLOADS ((num,
+        record_bytes - 32) uint8); the engine tags both under the 16-byte `key` on the GPU and
+        applies payload-delta || tag-delta."""
+        key = np.frombuffer(bytes(key), np.uint8).copy()
+        if key.size != 16:
+            raise ValueError("the tag key is 16 bytes")
+        idx, ip = self._index(file_index)
+        o, _, pitch = self._deltas(old, idx.size)
+        n, _, npitch = self._deltas(new, idx.size)
+        if pitch != npitch:
+            raise ValueError("old and new payloads of different lengths")
+        d_o = self.alloc_dev(max(1, o.size))
+        try:
+            d_n = self.alloc_dev(max(1, n.size))
+            try:
+                if idx.size:
+                    self.h2d(d_o, o.reshape(-1))
+                    self.h2d(d_n, n.reshape(-1))
+                self.update_across_mac_dev(idx, d_o, d_n, pitch, num_files, k, key)
+                self.sync()
+            finally:
+                self.free_dev(d_n)
+        finally:
+            self.free_dev(d_o)
+
+    def update_rows_dev(self, rows, d_delta, delta_pitch, stream=None):
+        idx, ip = self._index(rows)
+        check(self._lib.pir_engine_update_rows_dev(self._h, ip, idx.size, d_delta, delta_pitch,
+                                                   stream), "update_rows_dev")
+
+    def update_across_dev(self, file_index, d_delta, delta_pitch, num_files, k, stream=None):
+        """Asynchronous on `stream`: the indices (host) are read now, the deltas (device) on the
+        stream, after every answer enqueued before and before every later one."""
+        idx, ip = self._index(file_index)
+        check(self._lib.pir_engine_update_across_dev(self._h, ip, idx.size, d_delta, delta_pitch,
+                                                     num_files, k, stream), "update_across_dev")
+
+    def update_within_dev(self, file_index, d_delta, delta_pitch, num_files, file_bytes, k,
+                          party=0, hermite=False, stream=None):
+        idx, ip = self._index(file_index)
+        check(self._lib.pir_engine_update_within_dev(self._h, ip, idx.size, d_delta, delta_pitch,
+                                                     num_files, file_bytes, k, party,
+                                                     int(bool(hermite)), stream),
+              "update_within_dev")
+
+    def update_across_mac_dev(self, file_index, d_old, d_new, pitch, num_files, k, key,
+                              stream=None):
+        key = np.frombuffer(bytes(key), np.uint8).copy()
+        idx, ip = self._index(file_index)
+        check(self._lib.pir_engine_update_across_mac_dev(
+            self._h, ip, idx.size, d_old, d_new, pitch, num_files, k,
+            key.ctypes.data_as(ctypes.c_void_p), stream), "update_across_mac_dev")
+
     # -- answers ---------------------------------------------------------------------------
     def _check_key(self, key):
         k, kp = _buf(key)

@@ -145,6 +145,64 @@ int pir_engine_get_shard_row(pir_engine_t *e, uint64_t row, uint8_t *out);
 /* rows [row0, row0+nrows) back to the host, record_bytes per row, packed */
 int pir_engine_get_shard(pir_engine_t *e, uint64_t row0, uint64_t nrows, uint8_t *out);
 
+/* ---- live record updates: changed files patched into the resident shard, and into the fold
+ *      image, in place (k_update_rows) ----
+ * Every encoding above is linear over GF(2^8), so a file that changes from `old` to `new` changes
+ * its coded rows by coefficient * (old ^ new).  All forms therefore take DELTAS, old ^ new: the
+ * engine cannot recover `old` from a coded row.  After the call the shard equals, byte for byte,
+ * what the matching encode call gives from the new files (the coefficients are the encoders'
+ * own); the same record may appear more than once in a batch, and records that share a row or a
+ * block of 4 rows may come together.  Partition engines take the same global indices as the
+ * whole and skip the rows of other partitions.
+ * The fold image survives: an update is not a rewrite.  A valid image is patched with the rows
+ * and stays valid (pir_engine_fold_image(REPORT) still reports its size); without a valid image
+ * there is none afterwards either, but a pass that wanted one before the update still counts, so
+ * under $PIR_FOLD_IMAGE=1 the next sharing pass builds it; with $PIR_FOLD_IMAGE=0 only the rows
+ * are touched.
+ * Ordering: an update runs after every answer enqueued before it, on any stream, and before
+ * every answer enqueued after it.  The _dev forms are asynchronous on `stream` (NULL: the
+ * engine's): the index array (host memory) is read before the call returns, the deltas (device
+ * memory, any alignment, delta i at d_delta + i * delta_pitch) are read on the stream.  The forms
+ * without _dev take host deltas, staged through an engine buffer, and wait for the update.
+ * PIR_EINVAL, checked before any device call, the shard and the image untouched: null pointers
+ * with num > 0, num < 0, an index at or beyond num_files (growing the database changes encdb: a
+ * re-encode) or a row beyond the shard, k outside [1, 16], encdb beyond the domain, a pitch below
+ * the bytes read, hermite on an engine with partitions or with one row, record_bytes < 33 for the
+ * CheckMAC form.  num == 0: PIR_OK, nothing done. */
+/* engine row rows[i] ^= delta i (record_bytes each); rows are this engine's row numbers */
+int pir_engine_update_rows_dev(pir_engine_t *e, const uint64_t *rows, int num,
+                               const uint8_t *d_delta, uint64_t delta_pitch, void *stream);
+int pir_engine_update_rows(pir_engine_t *e, const uint64_t *rows, int num, const uint8_t *delta,
+                           uint64_t delta_pitch);
+/* file f = file_index[i] of an across-encoded database (pir_engine_encode_across_*): encdb =
+ * ceil(num_files / k), j = f / encdb, global row r = f % encdb; row r ^= gf_pow(party_index, j) *
+ * delta i (record_bytes) */
+int pir_engine_update_across_dev(pir_engine_t *e, const uint64_t *file_index, int num,
+                                 const uint8_t *d_delta, uint64_t delta_pitch, uint64_t num_files,
+                                 int k, void *stream);
+int pir_engine_update_across(pir_engine_t *e, const uint64_t *file_index, int num,
+                             const uint8_t *delta, uint64_t delta_pitch, uint64_t num_files,
+                             int k);
+/* file r = file_index[i] of a within-encoded database (pir_engine_encode_within_*): global row r
+ * ^= XOR_{j<k} gf_pow(party, j) * part j of delta i (file_bytes long, parts of record_bytes);
+ * party as for the encode (0: the engine's).  hermite != 0 (a Shamir engine: no partitions, N =
+ * rows / 2, num_files <= N): also row N + r ^= XOR_{odd j<k} gf_pow(party, j - 1) * part j
+ * (pir_engine_encode_hermite_*) */
+int pir_engine_update_within_dev(pir_engine_t *e, const uint64_t *file_index, int num,
+                                 const uint8_t *d_delta, uint64_t delta_pitch, uint64_t num_files,
+                                 uint32_t file_bytes, int k, int party, int hermite,
+                                 void *stream);
+int pir_engine_update_within(pir_engine_t *e, const uint64_t *file_index, int num,
+                             const uint8_t *delta, uint64_t delta_pitch, uint64_t num_files,
+                             uint32_t file_bytes, int k, int party, int hermite);
+/* CheckMAC setups, across-encoded: d_old / d_new hold the old and new PAYLOADS (record_bytes - 32
+ * bytes each, `pitch` apart, device memory); the engine tags both with HMAC-SHA256(key[16], .) on
+ * the GPU, forms payload-delta || tag-delta and applies pir_engine_update_across_dev */
+int pir_engine_update_across_mac_dev(pir_engine_t *e, const uint64_t *file_index, int num,
+                                     const uint8_t *d_old, const uint8_t *d_new, uint64_t pitch,
+                                     uint64_t num_files, int k, const uint8_t key[16],
+                                     void *stream);
+
 /* ---- answers, host buffers (synchronous; key_len bytes of key) ---- */
 /* result: num_rounds * record_bytes bytes, round a at result + a*record_bytes.  With a
  * communicator attached (pir_comm_attach) every rank receives the XOR over partitions. */
@@ -432,7 +490,8 @@ int pir_engine_reserve_queue(pir_engine_t *e, int num_keys);
  * wanted it (a shard rewritten between queries never pays a build), and only while a sixteenth
  * of the device's memory stays free afterwards -- else the answers run without it and
  * pir_engine_last_error says so once; 2 builds it wherever a pass can use it and fails where it
- * does not fit.  $PIR_FOLD_IMAGE_MAX_BYTES caps its size.  Every write to the shard drops it.
+ * does not fit.  $PIR_FOLD_IMAGE_MAX_BYTES caps its size.  Every rewrite of the shard (set_shard,
+ * fill, encode) drops it; a live update (pir_engine_update_*) patches it in place and keeps it.
  * op: report only, build now (synchronous; an error with $PIR_FOLD_IMAGE=0), or drop;
  * *bytes_held (may be NULL) = the bytes of a valid image afterwards, 0 without one. */
 enum { PIR_FOLD_IMAGE_REPORT = 0, PIR_FOLD_IMAGE_BUILD = 1, PIR_FOLD_IMAGE_DROP = 2 };
